@@ -1,7 +1,8 @@
 #!/usr/bin/env python
 """Headline benchmark: DeepFM training throughput on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dist uniform|zipf] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dist uniform|zipf] [--dump-outputs DIR]
+    python bench.py --full [...] [--no-cpu-baseline] [--no-extra]
 
 Workload (BASELINE.json configs[1], "C2"): deepfm_pipeline, 13 dense + 26
 categorical fields x 1M vocab each (table 26,000,013 x 16 fp32), MLP
@@ -9,10 +10,12 @@ categorical fields x 1M vocab each (table 26,000,013 x 16 fp32), MLP
 training step (embedding gather + FM + MLP fwd/bwd + log-loss + Adam over every
 table row) on a synthetic batch already resident in HBM (a fresh one per step,
 drawn on the device before the timed region).  The timed region replays the
-hipGraph of the step K times, bracketed by barrier + synchronize.
+hipGraph of the step K times, bracketed by barrier + synchronize.  A plain run
+stops there: it prints the result line (`value`, `ms_per_step`, ...) and, with
+--dump-outputs DIR, first writes what the last timed step computed as DIR/<name>.npy.
 
-Then, inside the same run, a few eager steps are bracketed per kernel with HIP
-events on the launch stream: those durations give the per-kernel algorithmic GB/s
+With --full, inside the same run, a few eager steps are then bracketed per kernel with
+HIP events on the launch stream: those durations give the per-kernel algorithmic GB/s
 and TFLOP/s (`kernels`) and the `roofline` of the dominant kernel.  At N=1 the other
 single-GPU BASELINE configurations (C3 deepfm_multi_cate, C5 wdl with the bf16
 tower) are timed the same way with fewer steps (`extra_workloads`), and rank 0 times
@@ -552,24 +555,64 @@ def dropin_fit(args, n_batches=24, warm=3):
     return out
 
 
-def run_workload(wl, args, world, rank, sharded, steps, warmup, age, ksteps, barrier, dist_ids=None):
+DUMP_MAX_ELEMS = 1 << 20     # per dumped array; larger ones are sampled (seeded)
+DUMP_TABLE_ROWS = 1 << 16    # table rows sampled (seeded) for the dump
+
+
+def dump_outputs(eng, B, loss, out_dir, sharded, seed=2019):
+    """--dump-outputs: what a caller of train_step holds after the last timed step, as
+    out_dir/<name>.npy (float32; the loss float64): the step's logits and scores, its loss, the
+    dense parameters in the reference layout and the table's (and first-order weights') rows at
+    DUMP_TABLE_ROWS seeded row numbers, caught up to the step (the lazy-exact flush: the same
+    values the dense sweep holds).  An array above DUMP_MAX_ELEMS elements is written as a seeded
+    sample of its elements, so the whole dump stays far below 64 MB.  The sharded engine dumps
+    this rank's logits, scores and loss only."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    rng = np.random.default_rng(seed)
+    out = {"logits": eng.z[:B].float().cpu().numpy(), "scores": eng.score[:B].float().cpu().numpy(),
+           "loss": np.array([loss], dtype=np.float64)}
+    if not sharded:
+        out.update(eng.dense_params())
+        sp, n = eng.spec, eng.N
+        rows = torch.from_numpy(np.sort(rng.choice(n, size=min(n, DUMP_TABLE_ROWS), replace=False))).to(eng.z.device)
+        eng.flush()
+        if eng.lazy:
+            rec = eng.rec[rows]
+            out["table_rows"] = rec[:, : sp.E].cpu().numpy()
+            if sp.fm:
+                out["first_order_rows"] = rec[:, sp.E].cpu().numpy()
+        else:
+            out["table_rows"] = eng.table[rows].cpu().numpy()
+            if eng.first is not None:
+                out["first_order_rows"] = eng.first[rows].cpu().numpy()
+    for name, a in out.items():
+        a = np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+        if a.size > DUMP_MAX_ELEMS:
+            a = a.reshape(-1)[np.sort(rng.choice(a.size, size=DUMP_MAX_ELEMS, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    log("dumped %d arrays of the last timed step to %s" % (len(out), out_dir))
+
+
+def run_workload(wl, args, world, rank, sharded, steps, warmup, age, ksteps, barrier, dist_ids=None, dump=None):
     """The workload on the default stream, or (DLAMD_MAIN_PRIORITY set, an A/B switch) on a
-    compute stream of that priority.  dist_ids: the id distribution (default --dist)."""
+    compute stream of that priority.  dist_ids: the id distribution (default --dist).
+    dump: directory for dump_outputs (after the timed steps), or None."""
     import torch
     pr = os.environ.get("DLAMD_MAIN_PRIORITY")
     if pr is None:
-        return _run_workload(wl, args, world, rank, sharded, steps, warmup, age, ksteps, barrier, dist_ids)
+        return _run_workload(wl, args, world, rank, sharded, steps, warmup, age, ksteps, barrier, dist_ids, dump)
     st = torch.cuda.Stream(priority=int(pr))
     st.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(st):
-        r = _run_workload(wl, args, world, rank, sharded, steps, warmup, age, ksteps, barrier, dist_ids)
+        r = _run_workload(wl, args, world, rank, sharded, steps, warmup, age, ksteps, barrier, dist_ids, dump)
     torch.cuda.current_stream().wait_stream(st)
     return r
 
 
-def _run_workload(wl, args, world, rank, sharded, steps, warmup, age, ksteps, barrier, dist_ids=None):
+def _run_workload(wl, args, world, rank, sharded, steps, warmup, age, ksteps, barrier, dist_ids=None, dump=None):
     """Build the engine of workload `wl`, age its table, time `steps` steps (hipGraph replay,
-    next batch prefetched), then `ksteps` eager steps bracketed per kernel by HIP events.
+    next batch prefetched), then (--full) `ksteps` eager steps bracketed per kernel by HIP events.
     Uniform ids: a fresh device-drawn batch every step (no batch repeats, so the model never
     memorises the set and the data-dependent paths see a real loss); zipf: 32 host-drawn batches
     cycled (the Zipf permutations are host-side)."""
@@ -667,6 +710,22 @@ def _run_workload(wl, args, world, rank, sharded, steps, warmup, age, ksteps, ba
     eng.check_error()
     loss = eng.loss()
     log("%s: %.4f ms/step, %.1f M samples/s, loss %.4f" % (wl, ms, value / 1e6, loss))
+    if dump:
+        dump_outputs(eng, B, loss, dump, sharded)
+
+    def done(out):
+        if sharded:
+            out["shard"] = {"cap": eng.cap, "overflows": getattr(eng, "overflows", 0), "report_lag": eng.lag,
+                            "all_reduce_serial": eng.ar_serial, "exchange_bytes_per_rank": eng.exchange_bytes()}
+            eng.exch.close()
+        return out
+
+    if not args.full:   # a plain run: the headline figure alone
+        out = done(dict(spec=spec, value=value, ms=ms, loss=loss, nb=nb, host_ms=host_ms, step_events=step_ev))
+        del eng, batches, done
+        torch.cuda.synchronize()
+        torch.cuda.empty_cache()
+        return out
 
     # ---- live per-kernel timing (HIP events on the launch stream), eager steps
     eng.prof = []
@@ -772,11 +831,8 @@ def _run_workload(wl, args, world, rank, sharded, steps, warmup, age, ksteps, ba
     out = dict(spec=spec, value=value, ms=ms, loss=loss, roofline=roof, gather=gather, flush=flush, kernels=kernels,
                kernel_sum=sum(k["us"] for k in kernels.values()), nb=nb, gemm_peak=gemm_peak, host_ms=host_ms,
                step_events=step_ev)
-    if sharded:
-        out["shard"] = {"cap": eng.cap, "overflows": getattr(eng, "overflows", 0), "report_lag": eng.lag,
-                        "all_reduce_serial": eng.ar_serial, "exchange_bytes_per_rank": eng.exchange_bytes()}
-        eng.exch.close()
-    del eng, batches
+    out = done(out)
+    del eng, batches, done
     torch.cuda.synchronize()
     torch.cuda.empty_cache()
     return out
@@ -842,6 +898,17 @@ def main():
     ap.add_argument("--batch", type=int, default=C2["B"])
     ap.add_argument("--vocab", type=int, default=0,
                     help="per-field vocab (default: 1M at N=1 = C2; 100M/26 at N>1 = C4's 100M-row table)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure everything beside the headline figure: per-kernel "
+                         "timings and the roofline, the lookup alone, the table flush, the measured HBM copy "
+                         "peak, the other workloads (see --no-extra) and the CPU baselines (see "
+                         "--no-cpu-baseline); without it the run only sets up, warms up, times --steps steps "
+                         "and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (logits, scores, loss, dense parameters, a "
+                         "seeded sample of table rows) as DIR/<name>.npy; the same arguments give the same "
+                         "inputs from run to run.  With --full the per-kernel steps then start from the "
+                         "caught-up table the dump leaves")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--workload", default="c2", choices=["c2", "c3", "c5"],
                     help="c2 DeepFM (the headline, default); c3 deepfm_multi_cate 6 multi-hot slots x 60; "
@@ -900,8 +967,10 @@ def main():
     wl = args.workload
     if wl == "c3" and sharded:
         raise SystemExit("--workload c3 is single-GPU here; the multi-GPU workloads are C4 (default) and C5")
+    full = args.full
     r = run_workload(wl, args, world, rank, sharded, args.steps, args.warmup, args.age_steps,
-                     min(args.steps, 10), barrier)
+                     min(args.steps, 10) if full else 0, barrier,
+                     dump=args.dump_outputs if rank == 0 else None)
     spec = r["spec"]
     B = args.batch
     # the other single-GPU BASELINE configurations, timed the same way with fewer steps, so the
@@ -909,7 +978,7 @@ def main():
     # (N > 1: the sharded Wide&Deep, C5 at N GPUs, after the sharded DeepFM C4)
     extra = {}
     others = ()
-    if not args.no_extra:
+    if full and not args.no_extra:
         if world == 1 and not sharded:
             others = tuple((w2, None) for w2 in ("c2", "c3", "c5") if w2 != wl)
             if args.dist == "uniform":   # both id distributions for the training step
@@ -942,7 +1011,7 @@ def main():
         except Exception as ex:   # reported, never fatal
             extra["c5"]["dropin_fit"] = {"error": repr(ex)}
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         log("cpu baseline (torch-CPU restatement)")
         torch.cuda.empty_cache()
         try:
@@ -954,7 +1023,7 @@ def main():
         except Exception as e:  # reported, never fatal
             cpu["c1"] = {"error": repr(e)}
     peak_meas = None
-    if rank == 0:
+    if full and rank == 0:
         try:
             peak_meas = hbm_peak_measured()
             log("measured HBM copy peak %.1f GB/s" % peak_meas["GB/s"])
@@ -989,30 +1058,37 @@ def main():
                        "parallelism": "dp%d" % world if not sharded else
                        "dp%d + row-sharded table (RCCL all-to-all lookup, all-reduce dense grads)" % world,
                        "id_dist": args.dist, "table_adam": args.adam},
-            "roofline": r["roofline"],
-            "cpu_baseline": cpu,
-            "gather_north_star": r["gather"],
-            "table_flush": r["flush"],
+            "full": full,
             "distinct_batches": r["nb"],
             "table_age_steps": args.age_steps,
-            "gemm_peak_tflops": round(r["gemm_peak"], 1),
-            "hbm_copy_measured": peak_meas,
-            "kernels": r["kernels"],
-            "kernel_sum_us_per_step": round(r["kernel_sum"], 1),
             "host_submit_ms_per_step": round(r["host_ms"], 4),
             **({"shard": r["shard"]} if r.get("shard") else {}),
             **({"step_events": r["step_events"]} if r.get("step_events") else {}),
             "loss": round(r["loss"], 6),
-            "extra_workloads": extra or None,
         }
+        if args.dump_outputs:
+            out["dumped_outputs"] = args.dump_outputs
+        if full:   # what the measurements after the timed steps found
+            out.update({
+                "roofline": r["roofline"],
+                "cpu_baseline": cpu,
+                "gather_north_star": r["gather"],
+                "table_flush": r["flush"],
+                "gemm_peak_tflops": round(r["gemm_peak"], 1),
+                "hbm_copy_measured": peak_meas,
+                "kernels": r["kernels"],
+                "kernel_sum_us_per_step": round(r["kernel_sum"], 1),
+                "extra_workloads": extra or None,
+            })
         os.write(json_fd, (json.dumps(out) + "\n").encode())
-        # the headline's own summary once more, last on stderr (the extra workloads, the CPU
-        # baseline and the C1 leg log after the headline's per-kernel line: a 4-KB tail drops it)
-        k = r["kernels"]
-        log("headline %s: %.4f ms/step, %.4g %s; per-kernel us/launch: %s" % (
-            out["config"]["workload"].split(":")[0], r["ms"], out["value"], out["unit"], ", ".join(
-                "%s %.0f%s" % (n, v["us"], "x%d" % v["launches"] if v["launches"] > 1 else "")
-                for n, v in sorted(k.items(), key=lambda kv: -kv[1]["us"] * kv[1]["launches"]))))
+        if full:
+            # the headline's own summary once more, last on stderr (the extra workloads, the CPU
+            # baseline and the C1 leg log after the headline's per-kernel line: a short tail drops it)
+            k = r["kernels"]
+            log("headline %s: %.4f ms/step, %.4g %s; per-kernel us/launch: %s" % (
+                out["config"]["workload"].split(":")[0], r["ms"], out["value"], out["unit"], ", ".join(
+                    "%s %.0f%s" % (n, v["us"], "x%d" % v["launches"] if v["launches"] > 1 else "")
+                    for n, v in sorted(k.items(), key=lambda kv: -kv[1]["us"] * kv[1]["launches"]))))
     if sharded:
         dist.destroy_process_group()
 

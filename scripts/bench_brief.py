@@ -1,4 +1,4 @@
-"""One-screen summary of a bench.py JSON line: headline, roofline, CPU baseline, the extra
+"""One-screen summary of a `bench.py --full` JSON line: headline, roofline, CPU baseline, the extra
 workloads and the slowest kernels of each.  usage: python scripts/bench_brief.py bench.json"""
 import json
 import sys
@@ -13,6 +13,8 @@ def main(path):
     d = json.loads(open(path).read().strip().splitlines()[-1])
     print("%s: %.4f ms/step, %.3g samples/s, n_gpus %s, %s, world %s" % (
         d["config"]["workload"], d["ms_per_step"], d["value"], d["n_gpus"], d["config"]["parallelism"], d.get("world")))
+    if "roofline" not in d:   # a plain run's line: the headline alone (the rest needs bench.py --full)
+        return
     r = d["roofline"]
     print("  roofline %s %s: %.4g %s = %.3f of peak, traffic %s" % (
         r.get("kernel"), r["bound"], r["achieved"], r["unit"], r["frac"], r.get("traffic")))

@@ -9,7 +9,7 @@ fi
 for wl in $4; do
   for arm in new old new old; do
     if [ $arm = new ]; then E="DLAMD_AB_ARM=new"; else E="$EV"; fi
-    env $E timeout -k 10 300 python bench.py --no-cpu-baseline --no-extra --workload $wl --steps 20 --warmup 5 > $OUT/bench_${wl}_$arm.json 2> $OUT/bench_${wl}_$arm.err || { tail -5 $OUT/bench_${wl}_$arm.err; exit 1; }
+    env $E timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-extra --workload $wl --steps 20 --warmup 5 > $OUT/bench_${wl}_$arm.json 2> $OUT/bench_${wl}_$arm.err || { tail -5 $OUT/bench_${wl}_$arm.err; exit 1; }
     python -c "
 import json;d=json.loads(open('$OUT/bench_${wl}_$arm.json').read().strip().splitlines()[-1]);k=d['kernels']
 print('$wl $arm', d['ms_per_step'], {n: k[n]['us'] for n in k if 'gemm' not in n and 'adam' not in n})"

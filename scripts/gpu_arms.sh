@@ -14,7 +14,7 @@ for rep in 1 2; do
       label=${arm%%=*}; envs=${arm#*=}; E=${envs//,/ }
       [ "$envs" = "$arm" ] && E=""
       f=$OUT/bench_${wl}_${label}_$rep
-      env $E timeout -k 10 300 python bench.py --no-cpu-baseline --no-extra --workload $wl --steps 20 --warmup 5 > $f.json 2> $f.err || { tail -5 $f.err; exit 1; }
+      env $E timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-extra --workload $wl --steps 20 --warmup 5 > $f.json 2> $f.err || { tail -5 $f.err; exit 1; }
       python -c "
 import json;d=json.loads(open('$f.json').read().strip().splitlines()[-1]);k=d['kernels'];g=d.get('gather_north_star') or {}
 la=g.get('lookup_alone') or {}

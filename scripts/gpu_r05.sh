@@ -31,7 +31,7 @@ for step in "$@"; do
       done
       for a in base $v base $v; do
         if [ $a = base ]; then E=""; else E=$a; fi
-        run c2_$a 300 env DLAMD_VARIANT=$E python bench.py --no-cpu-baseline --no-extra --steps 20
+        run c2_$a 300 env DLAMD_VARIANT=$E python bench.py --full --no-cpu-baseline --no-extra --steps 20
         grep '^{' $OUT/c2_$a.log | python -c "
 import json,sys;d=json.loads(sys.stdin.read().strip().splitlines()[-1]);k=d['kernels']
 print('$a', d['ms_per_step'], {n: k[n]['us'] for n in k if n.startswith('gemm')})" >> $OUT/c2_ab.txt
@@ -40,7 +40,7 @@ print('$a', d['ms_per_step'], {n: k[n]['us'] for n in k if n.startswith('gemm')}
       rest=${step#envab_}; var=${rest%%__*}; wl=${rest#*__}; dist=uniform
       case $wl in *_zipf) dist=zipf; wl=${wl%_zipf} ;; esac
       for a in 0 1 0 1; do
-        run ${var}_${wl}_${dist}_$a 300 env $var=$a python bench.py --workload $wl --dist $dist --no-cpu-baseline --no-extra --steps 20
+        run ${var}_${wl}_${dist}_$a 300 env $var=$a python bench.py --full --workload $wl --dist $dist --no-cpu-baseline --no-extra --steps 20
         grep '^{' $OUT/${var}_${wl}_${dist}_$a.log | python -c "
 import json,sys;d=json.loads(sys.stdin.read().strip().splitlines()[-1]);k=d['kernels']
 print('$var=$a $wl $dist', d['ms_per_step'], {n: k[n]['us'] for n in k})" >> $OUT/envab.txt
@@ -59,11 +59,11 @@ print('$var=$a $wl $dist', d['ms_per_step'], {n: k[n]['us'] for n in k})" >> $OU
       run bf16bench 200 python scripts/gemm_bf16_bench.py 20 ;;
     tests_*)   # tests_<pattern>: the GPU tests whose names match
       run tests_sel 900 $PYT tests -m gpu -k "${step#tests_}" ;;
-    bench) run bench 900 python bench.py ;;
-    benchsh) run benchsh 600 python bench.py --sharded --no-extra --no-cpu-baseline --steps 20 ;;
-    benchsh_c2) run benchsh_c2 600 python bench.py --sharded --no-extra --no-cpu-baseline --steps 20 --vocab 1000000 ;;
-    benchc2) run benchc2 600 python bench.py --no-extra --no-cpu-baseline --steps 20 ;;
-    benchc4single) run benchc4single 600 python bench.py --no-extra --no-cpu-baseline --steps 20 --vocab 3846154 ;;
+    bench) run bench 900 python bench.py --full ;;
+    benchsh) run benchsh 600 python bench.py --full --sharded --no-extra --no-cpu-baseline --steps 20 ;;
+    benchsh_c2) run benchsh_c2 600 python bench.py --full --sharded --no-extra --no-cpu-baseline --steps 20 --vocab 1000000 ;;
+    benchc2) run benchc2 600 python bench.py --full --no-extra --no-cpu-baseline --steps 20 ;;
+    benchc4single) run benchc4single 600 python bench.py --full --no-extra --no-cpu-baseline --steps 20 --vocab 3846154 ;;
     smoke) run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
     *) echo "unknown step $step" ;;
   esac

@@ -6,7 +6,7 @@ export TMPDIR=/tmp
 O=gpurun_out/r06i
 mkdir -p $O
 timeout -k 10 900 python -u -m pytest -x -q --timeout 300 --timeout-method thread tests/test_gpu_kernels.py tests/test_gpu_parity.py > $O/pytest.log 2>&1 || exit $?
-timeout -k 10 600 python -u bench.py --no-extra --no-cpu-baseline --steps 20 > $O/bench.json 2> $O/bench.log || exit $?
+timeout -k 10 600 python -u bench.py --full --no-extra --no-cpu-baseline --steps 20 > $O/bench.json 2> $O/bench.log || exit $?
 python - <<'PY' > $O/ab.txt
 import json
 d = json.loads([l for l in open("gpurun_out/r06i/bench.json") if l.strip()][-1])

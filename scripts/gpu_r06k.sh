@@ -7,7 +7,7 @@ O=gpurun_out/r06k
 mkdir -p $O
 timeout -k 10 900 python -u -m pytest -x -q --timeout 300 --timeout-method thread tests/test_gpu_kernels.py tests/test_gpu_parity.py > $O/pytest.log 2>&1 || exit $?
 for v in "" spw2 "" spw2; do
-  DLAMD_VARIANT=$v timeout -k 10 600 python -u bench.py --no-extra --no-cpu-baseline --steps 20 > $O/bench_${v:-main}.json 2>> $O/bench_${v:-main}.log || exit $?
+  DLAMD_VARIANT=$v timeout -k 10 600 python -u bench.py --full --no-extra --no-cpu-baseline --steps 20 > $O/bench_${v:-main}.json 2>> $O/bench_${v:-main}.log || exit $?
   python - "$O/bench_${v:-main}.json" "${v:-main}" >> $O/ab.txt <<'PY'
 import json, sys
 d = json.loads([l for l in open(sys.argv[1]) if l.strip()][-1])

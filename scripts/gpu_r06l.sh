@@ -12,6 +12,6 @@ for v in "" pa3 pa4 "" pa3 pa4; do
   DLAMD_VARIANT=$v timeout -k 10 200 python -u scripts/gemm_bf16_bench.py 20 2>/dev/null | grep -v amdgpu.ids | sed "s/^/[${v:-pa2}] /" >> $O/gemm_bf16.txt || exit $?
 done
 for v in "" pa3 pa4 "" pa3 pa4; do
-  DLAMD_VARIANT=$v timeout -k 10 300 python -u bench.py --workload c5 --no-extra --no-cpu-baseline --steps 30 > /dev/null 2>> $O/c5_${v:-pa2}.log || exit $?
+  DLAMD_VARIANT=$v timeout -k 10 300 python -u bench.py --full --workload c5 --no-extra --no-cpu-baseline --steps 30 > /dev/null 2>> $O/c5_${v:-pa2}.log || exit $?
   grep "per-kernel\|ms/step" $O/c5_${v:-pa2}.log | tail -2 | sed "s/^/[${v:-pa2}] /" >> $O/ab.txt
 done

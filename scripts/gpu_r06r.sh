@@ -8,6 +8,6 @@ mkdir -p $O
 timeout -k 10 900 python -u -m pytest -x -q --timeout 300 --timeout-method thread tests/test_gpu_kernels.py tests/test_gpu_parity.py -k "s3 or deepfm_pipeline or relu_bitmask" > $O/pytest.log 2>&1 || exit $?
 tail -2 $O/pytest.log
 for v in "" bitw0 "" bitw0; do
-  DLAMD_VARIANT=$v timeout -k 10 300 python -u bench.py --no-extra --no-cpu-baseline --steps 30 > /dev/null 2>> $O/c2_${v:-main}.log || exit $?
+  DLAMD_VARIANT=$v timeout -k 10 300 python -u bench.py --full --no-extra --no-cpu-baseline --steps 30 > /dev/null 2>> $O/c2_${v:-main}.log || exit $?
   grep "headline" $O/c2_${v:-main}.log | tail -1 | sed "s/^/[${v:-main}] /" >> $O/ab.txt
 done

@@ -15,7 +15,7 @@ for d in uniform zipf; do
   done
 done
 cat $O/lookup.txt
-timeout -k 10 400 python -u bench.py --no-extra --no-cpu-baseline --steps 20 > $O/bench.json 2> $O/bench.err || exit $?
+timeout -k 10 400 python -u bench.py --full --no-extra --no-cpu-baseline --steps 20 > $O/bench.json 2> $O/bench.err || exit $?
 python - <<PY
 import json
 d = json.loads(open("$O/bench.json").read().strip().splitlines()[-1])

@@ -7,7 +7,7 @@ O=gpurun_out/r06z2
 mkdir -p $O
 timeout -k 10 900 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread > $O/pytest.log 2>&1 || { tail -30 $O/pytest.log; exit 1; }
 tail -2 $O/pytest.log
-timeout -k 10 600 python -u bench.py > $O/bench.json 2> $O/bench.err || exit $?
+timeout -k 10 600 python -u bench.py --full > $O/bench.json 2> $O/bench.err || exit $?
 python - <<PY
 import json
 d = json.loads(open("$O/bench.json").read().strip().splitlines()[-1])

@@ -11,7 +11,7 @@ for d in uniform zipf; do
   done
 done
 for v in "" mw4 "" mw4; do
-  DLAMD_VARIANT=$v timeout -k 10 300 python -u bench.py --no-extra --no-cpu-baseline --steps 30 > /dev/null 2>> $O/c2_${v:-main}.log || exit $?
+  DLAMD_VARIANT=$v timeout -k 10 300 python -u bench.py --full --no-extra --no-cpu-baseline --steps 30 > /dev/null 2>> $O/c2_${v:-main}.log || exit $?
   grep "headline" $O/c2_${v:-main}.log | tail -1 | cut -c1-300 | sed "s/^/[${v:-main}] /" >> $O/ab.txt
 done
 cat $O/ab.txt

@@ -13,10 +13,10 @@ if [ "$MODE" = quick ]; then
   timeout -k 10 600 python -u -m pytest tests -m gpu --maxfail=8 -q -rf -p no:cacheprovider --timeout 300 --timeout-method thread \
     --deselect tests/test_gpu_fullsize.py --durations=10 > $OUT/pytest_quick.log 2>&1
   rc=$?; echo "pytest rc=$rc"; tail -15 $OUT/pytest_quick.log; [ $rc -eq 0 ] || exit $rc
-  timeout -k 10 300 python bench.py --workload c3 --no-extra --no-cpu-baseline --steps 10 > $OUT/c3.json 2> $OUT/c3.err
+  timeout -k 10 300 python bench.py --full --workload c3 --no-extra --no-cpu-baseline --steps 10 > $OUT/c3.json 2> $OUT/c3.err
   rc=$?; echo "c3 rc=$rc"; [ $rc -eq 0 ] || { tail -5 $OUT/c3.err; exit $rc; }
   python scripts/bench_brief.py $OUT/c3.json
-  timeout -k 10 300 python bench.py --workload c3 --dist zipf --no-extra --no-cpu-baseline --steps 10 > $OUT/c3z.json 2> $OUT/c3z.err
+  timeout -k 10 300 python bench.py --full --workload c3 --dist zipf --no-extra --no-cpu-baseline --steps 10 > $OUT/c3z.json 2> $OUT/c3z.err
   rc=$?; echo "c3 zipf rc=$rc"; [ $rc -eq 0 ] || { tail -5 $OUT/c3z.err; exit $rc; }
   python scripts/bench_brief.py $OUT/c3z.json
   exit 0
@@ -28,7 +28,7 @@ if [ "$MODE" = full ]; then
   rc=$?; echo "pytest rc=$rc"; tail -15 $OUT/pytest_full.log; exit $rc
 fi
 if [ "$MODE" = bench ]; then
-  timeout -k 10 600 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err
+  timeout -k 10 600 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err
   rc=$?; echo "bench rc=$rc"; [ $rc -eq 0 ] || { tail -5 $OUT/bench_default.err; exit $rc; }
   python scripts/bench_brief.py $OUT/bench_default.json
   exit 0
@@ -37,7 +37,7 @@ if [ "$MODE" = trace ]; then
   # kernel timeline of the hipGraph steps (workload $3, default c2)
   WL=${3:-c2}
   timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $OUT/trace_$WL -o trace -- \
-    python bench.py --no-extra --no-cpu-baseline --workload $WL --steps 10 --warmup 3 --age-steps 16 \
+    python bench.py --full --no-extra --no-cpu-baseline --workload $WL --steps 10 --warmup 3 --age-steps 16 \
     > $OUT/trace_$WL.log 2>&1
   rc=$?; echo "trace rc=$rc"; [ $rc -eq 0 ] || { tail -5 $OUT/trace_$WL.log; exit $rc; }
   f=$(ls $OUT/trace_$WL/*kernel_trace.csv 2>/dev/null | head -1)
@@ -49,7 +49,7 @@ if [ "$MODE" = hosttrace ]; then
   # kernels and HIP API calls of the hipGraph steps: host submission against the GPU at the boundary
   WL=${3:-c5}
   timeout -k 10 300 rocprofv3 --kernel-trace --hip-runtime-trace --output-format csv -d $OUT/htrace_$WL -o trace -- \
-    python bench.py --no-extra --no-cpu-baseline --workload $WL --steps 10 --warmup 3 --age-steps 16 \
+    python bench.py --full --no-extra --no-cpu-baseline --workload $WL --steps 10 --warmup 3 --age-steps 16 \
     > $OUT/htrace_$WL.log 2>&1
   rc=$?; echo "htrace rc=$rc"; [ $rc -eq 0 ] || { tail -5 $OUT/htrace_$WL.log; exit $rc; }
   k=$(find $OUT/htrace_$WL -name "*kernel_trace.csv" | head -1)
@@ -83,7 +83,7 @@ if [ "$MODE" = pfmid ]; then
     cfgs="c5:0 c5:1 c2:0 c2:1"; [ $rep -eq 3 ] && cfgs="c3:0 c3:1"
     for cfg in $cfgs; do
       IFS=: read wl e <<< "$cfg"
-      DLAMD_STEP_EVENTS=1 DLAMD_PF_MID=$e timeout -k 10 300 python bench.py --no-cpu-baseline --no-extra --workload $wl \
+      DLAMD_STEP_EVENTS=1 DLAMD_PF_MID=$e timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-extra --workload $wl \
         --steps 20 --warmup 5 > $OUT/mid_${wl}_$e.json 2> $OUT/mid_${wl}_$e.err || { tail -5 $OUT/mid_${wl}_$e.err; exit 1; }
       python -c "
 import json;d=json.loads(open('$OUT/mid_${wl}_$e.json').read().strip().splitlines()[-1])
@@ -126,7 +126,7 @@ if [ "$MODE" = stgap ]; then
     for wl in c5 c2; do
       for cfg in 1:0 1000:0 1:1; do
         IFS=: read ev rg <<< "$cfg"
-        DLAMD_STEP_EVENTS=1 DLAMD_STATUS_EVERY=$ev DLAMD_STATUS_RING=$rg timeout -k 10 300 python bench.py --no-cpu-baseline --no-extra \
+        DLAMD_STEP_EVENTS=1 DLAMD_STATUS_EVERY=$ev DLAMD_STATUS_RING=$rg timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-extra \
           --workload $wl --steps 30 --warmup 5 > $OUT/st_${wl}_$ev$rg.json 2> $OUT/st_${wl}_$ev$rg.err || { tail -5 $OUT/st_${wl}_$ev$rg.err; exit 1; }
         python -c "
 import json;d=json.loads(open('$OUT/st_${wl}_$ev$rg.json').read().strip().splitlines()[-1])
@@ -141,7 +141,7 @@ if [ "$MODE" = hotfold ]; then
   timeout -k 10 400 python -u -m pytest tests -m gpu -q -rf -k "hot or determin or lazy or prefetch or bad_id or zipf" \
     --deselect tests/test_gpu_fullsize.py -p no:cacheprovider --timeout 200 --timeout-method thread > $OUT/pytest_hot.log 2>&1
   rc=$?; echo "pytest rc=$rc: $(tail -1 $OUT/pytest_hot.log)"; [ $rc -eq 0 ] || { grep -E "^(FAILED|ERROR)" $OUT/pytest_hot.log; exit $rc; }
-  timeout -k 10 300 python bench.py --workload c3 --dist zipf --no-extra --no-cpu-baseline --steps 10 > $OUT/c3z.json 2> $OUT/c3z.err || { tail -5 $OUT/c3z.err; exit 1; }
+  timeout -k 10 300 python bench.py --full --workload c3 --dist zipf --no-extra --no-cpu-baseline --steps 10 > $OUT/c3z.json 2> $OUT/c3z.err || { tail -5 $OUT/c3z.err; exit 1; }
   python scripts/bench_brief.py $OUT/c3z.json
   bash scripts/gpu_ab_variant.sh ${TAG}_ab nofold "" "" "c2 c5"
   exit $?
@@ -170,7 +170,7 @@ if [ "$MODE" = pfmid2 ]; then
     for wl in $wls; do
       for cfg in 1:0 2:1 2:0; do
         IFS=: read dp e <<< "$cfg"
-        DLAMD_STEP_EVENTS=1 DLAMD_PF_DEPTH=$dp DLAMD_PF_MID=$e timeout -k 10 300 python bench.py --no-cpu-baseline --no-extra \
+        DLAMD_STEP_EVENTS=1 DLAMD_PF_DEPTH=$dp DLAMD_PF_MID=$e timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-extra \
           --workload $wl --steps 30 --warmup 5 > $OUT/m2_${wl}_$dp$e.json 2> $OUT/m2_${wl}_$dp$e.err || { tail -5 $OUT/m2_${wl}_$dp$e.err; exit 1; }
         python -c "
 import json;d=json.loads(open('$OUT/m2_${wl}_$dp$e.json').read().strip().splitlines()[-1])
@@ -211,7 +211,7 @@ if [ "$MODE" = nowait ]; then
   for rep in 1 2; do
     for cfg in c5:0 c5:1 c2:0 c2:1; do
       IFS=: read wl e <<< "$cfg"
-      DLAMD_PF_NOWAIT=$e timeout -k 10 300 python bench.py --no-cpu-baseline --no-extra --workload $wl \
+      DLAMD_PF_NOWAIT=$e timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-extra --workload $wl \
         --steps 20 --warmup 5 > $OUT/nw_${wl}_$e.json 2> $OUT/nw_${wl}_$e.err || { tail -5 $OUT/nw_${wl}_$e.err; exit 1; }
       python -c "
 import json;d=json.loads(open('$OUT/nw_${wl}_$e.json').read().strip().splitlines()[-1])
@@ -225,7 +225,7 @@ if [ "$MODE" = check ]; then
   # the GPU suite without the full-size tests, then C2 / C5 benches and a C2 trace
   bash scripts/gpu_r4.sh quick $TAG || exit $?
   for wl in c2 c5; do
-    timeout -k 10 300 python bench.py --no-cpu-baseline --no-extra --workload $wl --steps 20 --warmup 5 \
+    timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-extra --workload $wl --steps 20 --warmup 5 \
       > $OUT/b_$wl.json 2> $OUT/b_$wl.err || { tail -5 $OUT/b_$wl.err; exit 1; }
     python scripts/bench_brief.py $OUT/b_$wl.json
   done
@@ -237,7 +237,7 @@ if [ "$MODE" = status ]; then
   for rep in 1 2; do
     for cfg in c5:1 c5:16 c2:1 c2:16; do
       IFS=: read wl e <<< "$cfg"
-      DLAMD_STATUS_EVERY=$e timeout -k 10 300 python bench.py --no-cpu-baseline --no-extra --workload $wl \
+      DLAMD_STATUS_EVERY=$e timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-extra --workload $wl \
         --steps 20 --warmup 5 > $OUT/st_${wl}_$e.json 2> $OUT/st_${wl}_$e.err || { tail -5 $OUT/st_${wl}_$e.err; exit 1; }
       python -c "
 import json;d=json.loads(open('$OUT/st_${wl}_$e.json').read().strip().splitlines()[-1])
@@ -253,7 +253,7 @@ if [ "$MODE" = prio ]; then
     for cfg in c5:-1:x c5:-1:-1 c5:0:x c2:-1:x c2:-1:-1; do
       IFS=: read wl sp mp <<< "$cfg"
       if [ $mp = x ]; then MP=""; else MP="DLAMD_MAIN_PRIORITY=$mp"; fi
-      env DLAMD_SIDE_PRIORITY=$sp $MP timeout -k 10 300 python bench.py --no-cpu-baseline --no-extra --workload $wl \
+      env DLAMD_SIDE_PRIORITY=$sp $MP timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-extra --workload $wl \
         --steps 20 --warmup 5 > $OUT/pr_${wl}_${sp}_$mp.json 2> $OUT/pr_${wl}_${sp}_$mp.err || { tail -5 $OUT/pr_${wl}_${sp}_$mp.err; exit 1; }
       python -c "
 import json;d=json.loads(open('$OUT/pr_${wl}_${sp}_$mp.json').read().strip().splitlines()[-1])
@@ -269,13 +269,13 @@ if [ "$MODE" = pfeager ]; then
   for rep in 1 2; do
     for cfg in c5:0 c5:1 c2:0 c2:1; do
       IFS=: read wl e <<< "$cfg"
-      DLAMD_PF_EAGER=$e timeout -k 10 300 python bench.py --no-cpu-baseline --no-extra --workload $wl \
+      DLAMD_PF_EAGER=$e timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-extra --workload $wl \
         --steps 20 --warmup 5 > $OUT/pe_${wl}_$e.json 2> $OUT/pe_${wl}_$e.err || { tail -5 $OUT/pe_${wl}_$e.err; exit 1; }
       python -c "
 import json;d=json.loads(open('$OUT/pe_${wl}_$e.json').read().strip().splitlines()[-1])
 print('$wl pf_eager=$e', d['ms_per_step'], 'host', d.get('host_submit_ms_per_step'))"
     done
-    timeout -k 10 300 python bench.py --no-cpu-baseline --no-extra --workload c5 --no-prefetch --steps 20 --warmup 5 \
+    timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-extra --workload c5 --no-prefetch --steps 20 --warmup 5 \
       > $OUT/pe_c5_nopf.json 2> $OUT/pe_c5_nopf.err || exit 1
     python -c "
 import json;d=json.loads(open('$OUT/pe_c5_nopf.json').read().strip().splitlines()[-1])
@@ -292,7 +292,7 @@ if [ "$MODE" = pfdepth ]; then
   for rep in 1 2; do
     for cfg in c5:1:0 c5:2:0 c5:2:1 c2:1:0 c2:2:0; do
       IFS=: read wl d a <<< "$cfg"
-      DLAMD_PF_DEPTH=$d DLAMD_PF_AFTER=$a timeout -k 10 300 python bench.py --no-cpu-baseline --no-extra --workload $wl \
+      DLAMD_PF_DEPTH=$d DLAMD_PF_AFTER=$a timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-extra --workload $wl \
         --steps 20 --warmup 5 > $OUT/pf_${wl}_${d}_${a}.json 2> $OUT/pf_${wl}_${d}_${a}.err || { tail -5 $OUT/pf_${wl}_${d}_${a}.err; exit 1; }
       python -c "
 import json;d=json.loads(open('$OUT/pf_${wl}_${d}_${a}.json').read().strip().splitlines()[-1])
@@ -306,7 +306,7 @@ if [ "$MODE" = pfab ]; then
   # the next batch's prefetch submitted before (0) or after (1) the step's own graph
   for wl in c5 c2; do
     for a in 0 1 0 1; do
-      DLAMD_PF_AFTER=$a timeout -k 10 300 python bench.py --no-cpu-baseline --no-extra --workload $wl --steps 20 \
+      DLAMD_PF_AFTER=$a timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-extra --workload $wl --steps 20 \
         --warmup 5 > $OUT/pf_${wl}_$a.json 2> $OUT/pf_${wl}_$a.err || { tail -5 $OUT/pf_${wl}_$a.err; exit 1; }
       python -c "
 import json;d=json.loads(open('$OUT/pf_${wl}_$a.json').read().strip().splitlines()[-1])
@@ -331,10 +331,10 @@ if [ "$MODE" = bwddiag ]; then
     if [ $V = new ]; then VV=""; else VV=$V; fi
     args="--no-cpu-baseline --no-extra --workload c2"
     DLAMD_VARIANT=$VV timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $W/prof_fetch -o fetch -- \
-      python bench.py --steps 3 --warmup 1 $args > $W/prof_fetch.log 2>&1
+      python bench.py --full --steps 3 --warmup 1 $args > $W/prof_fetch.log 2>&1
     rc=$?; echo "$V fetch rc=$rc"; [ $rc -eq 0 ] || exit $rc
     DLAMD_VARIANT=$VV timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $W/prof_write -o write -- \
-      python bench.py --steps 3 --warmup 1 $args > $W/prof_write.log 2>&1
+      python bench.py --full --steps 3 --warmup 1 $args > $W/prof_write.log 2>&1
     rc=$?; echo "$V write rc=$rc"; [ $rc -eq 0 ] || exit $rc
     python scripts/pmc_summary.py $W $W/pmc_summary.json c2 > $W/summary.txt && grep -i "bwd\|gather" $W/summary.txt | head -6
   done

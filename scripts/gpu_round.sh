@@ -21,7 +21,7 @@ if [ "$MODE" = suite ]; then
   unset DLAMD_TEST_STATS
   timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1
   rc=$?; echo "smoke rc=$rc"; tail -3 $OUT/smoke.log; [ $rc -eq 0 ] || exit $rc
-  timeout -k 10 600 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err
+  timeout -k 10 600 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err
   rc=$?; echo "bench rc=$rc"; [ $rc -eq 0 ] || { tail -5 $OUT/bench_default.err; exit $rc; }
   python scripts/bench_brief.py $OUT/bench_default.json
   exit 0
@@ -33,13 +33,13 @@ if [ "$MODE" = prof ]; then
     mkdir -p $W
     args="--no-cpu-baseline --no-extra --workload $wl"
     timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $W/prof_trace -o trace -- \
-      python bench.py --steps 10 --warmup 3 $args > $W/prof_trace.log 2>&1
+      python bench.py --full --steps 10 --warmup 3 $args > $W/prof_trace.log 2>&1
     rc=$?; echo "$wl trace rc=$rc"; [ $rc -eq 0 ] || exit $rc
     timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $W/prof_fetch -o fetch -- \
-      python bench.py --steps 3 --warmup 1 $args > $W/prof_fetch.log 2>&1
+      python bench.py --full --steps 3 --warmup 1 $args > $W/prof_fetch.log 2>&1
     rc=$?; echo "$wl fetch rc=$rc"; [ $rc -eq 0 ] || exit $rc
     timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $W/prof_write -o write -- \
-      python bench.py --steps 3 --warmup 1 $args > $W/prof_write.log 2>&1
+      python bench.py --full --steps 3 --warmup 1 $args > $W/prof_write.log 2>&1
     rc=$?; echo "$wl write rc=$rc"; [ $rc -eq 0 ] || exit $rc
     python scripts/pmc_summary.py $W $OUT/pmc_summary_$wl.json $wl > $W/summary.txt && head -12 $W/summary.txt
   done
@@ -50,7 +50,7 @@ fi
 if [ "$MODE" = rehearse ]; then
   # the multi-rank bench flow on one GPU: bench.py --gpus 2 starts its two ranks itself
   # (gloo-staged exchange, both ranks on device 0), then the same under the driver's launcher form
-  DLAMD_BENCH_BACKEND=gloo timeout -k 10 600 python bench.py --gpus 2 --steps 5 --warmup 2 --age-steps 8 \
+  DLAMD_BENCH_BACKEND=gloo timeout -k 10 600 python bench.py --full --gpus 2 --steps 5 --warmup 2 --age-steps 8 \
     --extra-steps 3 > $OUT/bench_gpus2.json 2> $OUT/bench_gpus2.err
   rc=$?; echo "bench --gpus 2 rc=$rc"; [ $rc -eq 0 ] || { tail -20 $OUT/bench_gpus2.err; exit $rc; }
   python scripts/bench_brief.py $OUT/bench_gpus2.json

@@ -1,5 +1,5 @@
 cd "$GRAFT_REPO_ROOT"; export TMPDIR=/tmp; OUT=gpurun_out/shm; mkdir -p $OUT
-run() { local n=$1; shift; timeout -k 10 300 python bench.py --no-cpu-baseline --no-extra "$@" > $OUT/$n.json 2> $OUT/$n.err || { tail -5 $OUT/$n.err; return 1; }
+run() { local n=$1; shift; timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-extra "$@" > $OUT/$n.json 2> $OUT/$n.err || { tail -5 $OUT/$n.err; return 1; }
   python -c "
 import json;d=json.loads(open('$OUT/$n.json').read().strip().splitlines()[-1]);k=d['kernels']
 print('$n', d['ms_per_step'], {x: k[x]['us'] for x in k})"; }

@@ -8,7 +8,7 @@ fi
 for wl in c3 c2; do
   for arm in new $VAR; do
     if [ $arm = new ]; then E="DLAMD_AB_ARM=new"; else E="DLAMD_VARIANT=$VAR"; fi
-    env $E timeout -k 10 300 python bench.py --no-cpu-baseline --no-extra --dist zipf --workload $wl --steps 10 --warmup 3 > $OUT/zipf_${wl}_$arm.json 2> $OUT/zipf_${wl}_$arm.err || { tail -5 $OUT/zipf_${wl}_$arm.err; exit 1; }
+    env $E timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-extra --dist zipf --workload $wl --steps 10 --warmup 3 > $OUT/zipf_${wl}_$arm.json 2> $OUT/zipf_${wl}_$arm.err || { tail -5 $OUT/zipf_${wl}_$arm.err; exit 1; }
     python -c "
 import json;d=json.loads(open('$OUT/zipf_${wl}_$arm.json').read().strip().splitlines()[-1]);k=d['kernels']
 print('$wl $arm', d['ms_per_step'], {n: k[n]['us'] for n in ('embed_bwd', 'rec_gather', 'index_build') if n in k})"

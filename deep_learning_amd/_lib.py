@@ -67,7 +67,7 @@ def reg_sum(q):
 LOSS_ACC_SLOTS = 65536
 
 P = C.c_void_p
-I32, I64, U64, F = C.c_int32, C.c_int64, C.c_uint64, C.c_float
+I32, I64, U32, U64, F = C.c_int32, C.c_int64, C.c_uint32, C.c_uint64, C.c_float
 LP = C.POINTER(EmbLayout)
 
 # name -> (restype, argtypes); the authoritative list of exported entry points
@@ -108,6 +108,9 @@ SIGNATURES = {
     "dl_s3_kperm": (I32, []),
     "dl_gemm_s3_nt": (I32, [I32, I32, I32, P, I32, P, I32, I64, P, I32, I32, P, I32, P]),
     "dl_gemm_s3_nt_bits": (I32, [I32, I32, I32, P, I32, P, I32, I64, P, I32, I32, P, I32, P, I32, P]),
+    "dl_gemm_s3_nt_drop": (I32, [I32, I32, I32, P, I32, P, I32, I64, P, I32, I32, P, I32, P, I32, U32, F, U64, I32, P,
+                                 P]),
+    "dl_dropout_apply": (I32, [P, I32, I32, I32, U32, F, U64, I32, P, P, P]),
     "dl_gemm_s3_nt_gather": (I32, [I32, I32, I32, P, I32, P, I64, I32, P, I32, I64, I32, I32, I32, P, I32, I64, P,
                                    I32, I32, P, I32, P]),
     "dl_gemm_s3_nt_gather_rows": (I32, [I32, I32, I32, P, I32, P, I64, I32, P, I32, I32, I32, I32, P, I32, I64, P,

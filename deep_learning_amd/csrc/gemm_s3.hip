@@ -21,6 +21,7 @@
 //       MFMA fragments by CDNA4's transposing ds_read_b64_tr_b16.  Block 128 x 416
 //       (8 waves x 32 rows x 13 column fragments).
 #include "common.h"
+#include "philox.h"
 #include <cstdlib>
 #include <type_traits>
 
@@ -119,6 +120,13 @@ struct S3Params {
   // (the table form, dl_gemm_s3_nt_gather_tab) the rows' byte offsets already resolved by the
   // lookup (common.h kGtab*): the block stages its part of the table as it stands
   const uint32_t* gofs;
+  // NT dropout (dl_gemm_s3_nt_drop; appended, so the other forms' argument offsets stand): the
+  // keep threshold, the 1/keep factor, the Philox key (the seed's halves), the tensor's layer
+  // number and the optimizer block whose opt[7] is the step (include/dlamd.h "Dropout")
+  uint32_t drop_thr;
+  float drop_inv;
+  uint32_t drop_k0, drop_k1, drop_layer;
+  const float* opt;
 };
 
 // S3_MASKBITS: the ReluGrad mask from the forward's bitmask (bit c & 15 of halfword
@@ -227,7 +235,11 @@ __device__ __forceinline__ void nt_rd3(uint32_t a, shortx8& h, shortx8& m, short
 // pieces into p.a_store (x0) as they split them, for the weight gradient that streams x0 later —
 // four 16-B stores a lane and step, past the range (dropped) where there is nothing to write,
 // so every wave's vector-memory queue keeps one straight-line count.
-template <int EPI, bool DIRECT = false, bool GATHER = false, bool STORE_A = false>
+// DROP (dl_gemm_s3_nt_drop; S3_RELU / S3_MASKBITS): dropout in the epilogue.  S3_RELU draws the
+// keep bits of the four consecutive columns a lane stores from one Philox call (philox.h
+// drop_keep4), stores keep ? relu * inv : 0 and ANDs the keep bits into the sign bitmask;
+// S3_MASKBITS reads that combined mask and scales what it lets through by inv (no RNG).
+template <int EPI, bool DIRECT = false, bool GATHER = false, bool STORE_A = false, bool DROP = false>
 __global__ __launch_bounds__(512) void gemm_s3_nt_kernel(S3Params p) {
   extern __shared__ __attribute__((aligned(16))) unsigned short lds[];   // [3 bufs][3 planes][BN][32]
   constexpr int NW = 8, BM = kNtBM, DMAW = kNtDmaW;
@@ -648,6 +660,12 @@ __global__ __launch_bounds__(512) void gemm_s3_nt_kernel(S3Params p) {
     // lane (kq, cl): acc[a][f][j] = C[r0 + 16a + cl][j0 + 16f + 4kq + j].  Stores go through a
     // buffer descriptor: a piece past M or N gets an offset past its range and is dropped.
     const auto c_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.C, (short)0, p.M * p.ldc * 4, 0x00020000);
+    [[maybe_unused]] uint32_t d_step = 0;
+    [[maybe_unused]] uint2 d_key = make_uint2(0u, 0u);
+    if constexpr (DROP && EPI == S3_RELU) {
+      d_step = drop_step(p.opt);
+      d_key = make_uint2(p.drop_k0, p.drop_k1);
+    }
 #pragma unroll
     for (int a = 0; a < 2; ++a) {
       const int row = r0 + 16 * a + cl;
@@ -658,18 +676,29 @@ __global__ __launch_bounds__(512) void gemm_s3_nt_kernel(S3Params p) {
         if (EPI == S3_RELU) {
           v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f);
         }
+        [[maybe_unused]] uint32_t kb = 0xFu;
+        if constexpr (DROP && EPI == S3_RELU) {   // the lane's four columns are one Philox group
+          kb = drop_keep4((uint32_t)row, (uint32_t)col >> 2, p.drop_layer, d_step, d_key, p.drop_thr);
+          v[0] = (kb & 1u) ? v[0] * p.drop_inv : 0.f; v[1] = (kb & 2u) ? v[1] * p.drop_inv : 0.f;
+          v[2] = (kb & 4u) ? v[2] * p.drop_inv : 0.f; v[3] = (kb & 8u) ? v[3] * p.drop_inv : 0.f;
+        }
         if constexpr (EPI == S3_MASKBITS) {   // halfword (j0 >> 4) + f of the row, bits 4kq .. 4kq + 3
           const int hi = (j0 >> 4) + f - 2 * (j0 >> 5);
           const uint32_t m = (mw[a][hi >> 1] >> (16 * (hi & 1) + 4 * kq)) & 0xFu;
           v[0] = (m & 1u) ? v[0] : 0.f; v[1] = (m & 2u) ? v[1] : 0.f;
           v[2] = (m & 4u) ? v[2] : 0.f; v[3] = (m & 8u) ? v[3] : 0.f;
+          if constexpr (DROP) {
+            v[0] *= p.drop_inv; v[1] *= p.drop_inv; v[2] *= p.drop_inv; v[3] *= p.drop_inv;
+          }
         }
         const bool ok = row < p.M && col + 4 <= p.N;
         const uint32_t off = ok ? 4u * (uint32_t)(row * p.ldc + col) : 0x80000000u;
         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(s3_u32x4_t, v), c_rsrc, (int)off, 0, 0);
         if (EPI == S3_RELU && p.bits) {   // the sign bitmask: row's 16 bits of fragment f from 4 lanes
-          uint32_t hw = (uint32_t)((acc[a][f][0] > 0.f) | ((acc[a][f][1] > 0.f) << 1) | ((acc[a][f][2] > 0.f) << 2) |
-                                   ((acc[a][f][3] > 0.f) << 3)) << (4 * kq);
+          uint32_t nib = (uint32_t)((acc[a][f][0] > 0.f) | ((acc[a][f][1] > 0.f) << 1) | ((acc[a][f][2] > 0.f) << 2) |
+                                    ((acc[a][f][3] > 0.f) << 3));
+          if constexpr (DROP) nib = col < p.N ? nib & kb : 0u;   // (N % 4 == 0: a lane's columns are all in or all out)
+          uint32_t hw = nib << (4 * kq);
           hw |= (uint32_t)__shfl_xor((int)hw, 16, 64);
           hw |= (uint32_t)__shfl_xor((int)hw, 32, 64);
           const int h = (j0 >> 4) + f;
@@ -716,6 +745,52 @@ __global__ __launch_bounds__(512) void gemm_s3_nt_kernel(S3Params p) {
       for (int j = 0; j < 4; ++j) tile[(4 * kq + j) * kNtEP + 16 * f + cl] = acc[h][f][j];
     __builtin_amdgcn_s_waitcnt(0xc07f);             // lgkmcnt(0): this wave's tile writes landed
     __builtin_amdgcn_wave_barrier();
+    if constexpr (DROP) {
+      // The dropout form of the half's stores.  S3_RELU: a piece's four columns are one Philox
+      // group; its four combined bits (relu > 0 and kept, columns past N clear) meet the other
+      // three pieces of their halfword in the neighbouring lanes (q % 4 == lane % 4, and a row
+      // holds a multiple of four pieces), whose first lane stores it.  S3_MASKBITS: times inv.
+      const uint32_t d_step = EPI == S3_RELU ? drop_step(p.opt) : 0u;
+      const uint2 d_key = make_uint2(p.drop_k0, p.drop_k1);
+#pragma unroll
+      for (int it = 0; it < NIT; ++it) {
+        const int q = lane + 64 * it;
+        const int rl = q / VPR, pc = q % VPR;
+        const int row = r0 + 16 * h + rl, col = j0 + 4 * pc;
+        const bool in = q < 16 * VPR && row < p.M && col < p.N;
+        uint32_t nib = 0;
+        if (in) {
+          const float4 v = *reinterpret_cast<const float4*>(tile + rl * kNtEP + 4 * pc);
+          float e4[4] = {v.x, v.y, v.z, v.w};
+          if (EPI == S3_RELU) {
+            const uint32_t kb = drop_keep4((uint32_t)row, (uint32_t)col >> 2, p.drop_layer, d_step, d_key, p.drop_thr);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+              const float r = fmaxf(e4[e], 0.f);
+              const bool k = (kb >> e) & 1u;
+              nib |= (uint32_t)(k && r > 0.f && col + e < p.N) << e;
+              e4[e] = k ? r * p.drop_inv : 0.f;
+            }
+          } else {
+            const uint32_t m = mb[EPI == S3_MASKBITS ? it : 0];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) e4[e] = ((m >> e) & 1u) ? e4[e] * p.drop_inv : 0.f;
+          }
+          float* dst = p.C + (long long)row * p.ldc + col;
+          if (col + 4 <= p.N && (reinterpret_cast<uintptr_t>(dst) & 15) == 0) {
+            *reinterpret_cast<float4*>(dst) = make_float4(e4[0], e4[1], e4[2], e4[3]);
+          } else {
+            for (int e = 0; e < 4 && col + e < p.N; ++e) dst[e] = e4[e];
+          }
+        }
+        if (EPI == S3_RELU && p.bits) {   // uniform: every lane takes part in the exchange
+          uint32_t hv = nib << (4 * (pc & 3));
+          hv |= (uint32_t)__shfl_xor((int)hv, 1, 64);
+          hv |= (uint32_t)__shfl_xor((int)hv, 2, 64);
+          if (in && (pc & 3) == 0) p.bits[(long long)row * p.ldbits + (j0 >> 4) + (pc >> 2)] = (uint16_t)hv;
+        }
+      }
+    } else {
 #pragma unroll
     for (int it = 0; it < NIT; ++it) {
       const int q = lane + 64 * it;
@@ -748,10 +823,11 @@ __global__ __launch_bounds__(512) void gemm_s3_nt_kernel(S3Params p) {
         }
       }
     }
+    }
     // the forward's sign bitmask, straight from the accumulators (after the half's stores are
     // issued, so the ballots run while they drain): ballot j of fragment f holds
     // rows 4kq + j (kq = bit / 16) x columns 16f + (bit % 16); lane r < 16 stores row r's halfword
-    if (EPI == S3_RELU && p.bits) {
+    if (EPI == S3_RELU && p.bits && !DROP) {
 #pragma unroll
       for (int f = 0; f < kNtNF; ++f) {
         const uint64_t b0 = __ballot(acc[h][f][0] > 0.f), b1 = __ballot(acc[h][f][1] > 0.f);
@@ -1371,6 +1447,34 @@ extern "C" int dl_gemm_s3_nt_bits(int32_t M, int32_t N, int32_t K, const float* 
   else if (epi == S3_MASK) hipLaunchKernelGGL(gemm_s3_nt_kernel<S3_MASK>, dim3(tiles), dim3(512), kNtLds, s, p);
   else hipLaunchKernelGGL(gemm_s3_nt_kernel<S3_MASKBITS>, dim3(tiles), dim3(512), kNtLds, s, p);
   DL_RETURN_LAUNCH("dl_gemm_s3_nt");
+}
+
+extern "C" int dl_gemm_s3_nt_drop(int32_t M, int32_t N, int32_t K, const float* A, int32_t lda, const uint16_t* Bp,
+                                  int32_t ldb, int64_t b_plane, float* C, int32_t ldc, int32_t epi, const float* mask,
+                                  int32_t ldm, uint16_t* bits, int32_t ldbits, uint32_t keep_thr, float inv,
+                                  uint64_t seed, int32_t layer, const float* opt, void* stream) {
+  if (int rc = s3_nt_check(M, N, K, A, lda, Bp, ldb, b_plane, C, ldc, epi, mask, bits, ldbits)) return rc;
+  DL_CHECK_ARG(epi == S3_RELU || epi == S3_MASKBITS, "dropout goes with the relu / bitmask epilogues (epi %d)", epi);
+  DL_CHECK_ARG(opt, "opt is NULL");
+  DL_CHECK_ARG(layer >= 0 && inv >= 1.f && inv < 3.4e38f, "bad dropout layer %d / factor %g", layer, (double)inv);
+  if (M == 0 || N == 0) return 0;
+  S3Params p{};
+  p.A = A; p.B = Bp; p.C = C; p.mask = mask;
+  p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldb = ldb; p.ldc = ldc; p.ldm = ldm; p.b_plane = b_plane;
+  p.bits = bits; p.ldbits = ldbits;
+  p.drop_thr = keep_thr; p.drop_inv = inv; p.drop_k0 = (uint32_t)seed; p.drop_k1 = (uint32_t)(seed >> 32);
+  p.drop_layer = (uint32_t)layer; p.opt = opt;
+  hipStream_t s = as_stream(stream);
+  const bool direct = s3_nt_direct(M, N, ldc, epi, bits, ldbits);
+  const int tiles = (int)(ceil_div(M, kNtBM) * ceil_div(N, kNtBN));
+#define DL_S3D(E_, D_) hipLaunchKernelGGL((gemm_s3_nt_kernel<E_, D_, false, false, true>), dim3(tiles), dim3(512), kNtLds, s, p)
+  if (direct) {
+    if (epi == S3_RELU) DL_S3D(S3_RELU, true);
+    else DL_S3D(S3_MASKBITS, true);
+  } else if (epi == S3_RELU) DL_S3D(S3_RELU, false);
+  else DL_S3D(S3_MASKBITS, false);
+#undef DL_S3D
+  DL_RETURN_LAUNCH("dl_gemm_s3_nt_drop");
 }
 
 static int s3_nt_gather_launch(int32_t M, int32_t N, int32_t K, const float* A, int32_t lda, const float* table,

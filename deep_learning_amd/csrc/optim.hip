@@ -9,6 +9,7 @@
 // reset) for rows the step touched, which a uint8 flag per row records — an
 // untouched row's gradient is exactly zero, so the result is the dense one.
 #include "common.h"
+#include "philox.h"
 
 namespace dl {
 
@@ -456,20 +457,7 @@ __global__ void clear_touched_kernel(uint8_t* touched, long long n) {
 }
 
 // ---------------------------------------------------------------------------
-// Philox-4x32-10 counter-based RNG
-__device__ __forceinline__ uint4 philox(uint4 c, uint2 k) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const unsigned long long p0 = (unsigned long long)0xD2511F53u * c.x;
-    const unsigned long long p1 = (unsigned long long)0xCD9E8D57u * c.z;
-    c = make_uint4((unsigned)(p1 >> 32) ^ c.y ^ k.x, (unsigned)p1, (unsigned)(p0 >> 32) ^ c.w ^ k.y,
-                   (unsigned)p0);
-    k.x += 0x9E3779B9u;
-    k.y += 0xBB67AE85u;
-  }
-  return c;
-}
-
+// Counter-based init (Philox-4x32-10: philox.h)
 __global__ __launch_bounds__(256) void init_random_kernel(float* p, long long n, int dist, float mean,
                                                           float scale, unsigned long long seed,
                                                           unsigned long long offset) {

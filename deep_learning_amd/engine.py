@@ -70,11 +70,15 @@ class ModelSpec:
     cate_index_size (reference `cate_feats_size`), hidden units, multi_ranges
     [[start, end, name], ...] (multi-hot slots, relative to the multi block), Fw wide
     ids (wdl), lr, l2, decay_steps/decay_rate (exponential_decay), Adam betas/eps.
+    dropout_keep_deep: the reference's keep probabilities of the deep tower (tf.nn.dropout after
+    the tower input and after every ReLU layer, deepfm_pipeline.py:148-153): len(hidden) + 1
+    values in (0, 1], a longer list truncated (the reference's default holds 5 entries for 3
+    layers); None or all ones: no dropout.
     """
 
     def __init__(self, model, C=13, V=0, S=26, E=16, cate_index_size=1000, hidden=(400, 400, 400),
                  multi_ranges=(), Fw=0, lr=0.001, l2=1e-5, decay_steps=10000000, decay_rate=0.9,
-                 beta1=0.9, beta2=0.999, eps=1e-8, logloss_eps=1e-7, tower="f32"):
+                 beta1=0.9, beta2=0.999, eps=1e-8, logloss_eps=1e-7, tower="f32", dropout_keep_deep=None):
         if model not in FAMILIES:
             raise ValueError("unsupported model %r" % model)
         fam = FAMILIES[model]
@@ -93,6 +97,23 @@ class ModelSpec:
         if tower not in ("f32", "bf16"):
             raise ValueError("tower must be 'f32' or 'bf16'")
         self.tower = tower      # bf16: the deep tower's GEMMs on bf16 MFMA (config C5), fp32 master weights
+        if dropout_keep_deep is not None:
+            keep = [float(k) for k in dropout_keep_deep]
+            n = len(self.hidden) + 1
+            if len(keep) < n:
+                raise ValueError("dropout_keep_deep needs %d values (the tower input + %d layers), got %d"
+                                 % (n, n - 1, len(keep)))
+            keep = keep[:n]
+            if not all(0.0 < k <= 1.0 for k in keep):
+                raise ValueError("dropout_keep_deep values must lie in (0, 1], got %r" % (keep,))
+            dropout_keep_deep = keep
+        self.dropout_keep_deep = dropout_keep_deep
+
+    @property
+    def dropout(self):
+        """The keep probabilities [tower input, layer 0, ...] when any is below 1, else None."""
+        k = self.dropout_keep_deep
+        return k if k is not None and any(x < 1.0 for x in k) else None
 
     @property
     def fm(self):
@@ -227,6 +248,27 @@ class CTREngine:
             raise _lib.DLError("CTREngine needs a HIP device (no CPU fallback)")
         _lib.lib()
         self.spec = sp = spec
+        # dropout of the deep tower (ModelSpec.dropout_keep_deep): in the s3 epilogues, whose
+        # combined (sign & keep) bitmask the dX GEMMs read; the mask's seed is the engine's
+        self.seed = int(seed)
+        self.drop = sp.dropout
+        if self.drop:
+            if sp.tower == "bf16":
+                raise ValueError("dropout_keep_deep: not supported with tower='bf16' (the dropout epilogues are "
+                                 "the f32 s3 tower's)")
+            if gemm == "f32":
+                raise ValueError("dropout_keep_deep: not supported with gemm='f32' (the dropout epilogues are "
+                                 "the s3 GEMMs')")
+            if os.environ.get("DLAMD_RELU_BITS", "1") == "0":
+                raise ValueError("dropout_keep_deep: not supported with DLAMD_RELU_BITS=0 (the dX GEMMs read the "
+                                 "keep bits from the forward's bitmask)")
+            if type(self) is not CTREngine:
+                raise ValueError("dropout_keep_deep: not supported by %s (the mask is indexed by the local "
+                                 "row number; a sharded batch needs global rows)" % type(self).__name__)
+            if sp.fm and sp.M and self.drop[0] < 1.0:
+                raise ValueError("dropout_keep_deep: input dropout (keep[0] < 1) is not supported for FM models "
+                                 "with multi-hot slots (their FM backward reads the pooled vectors from x0, "
+                                 "which the input dropout overwrites)")
         self.dev = torch.device(device)
         self.B = max_batch
         dev = self.dev
@@ -834,6 +876,8 @@ class CTREngine:
         if (os.environ.get("DLAMD_FUSED_GATHER", "1") == "0" or not self.s3 or self.bf or not self.lazy
                 or type(self) is not CTREngine or self.fwd_rec or self.fwd_scatter):
             return False
+        if self.drop:   # the plain first layer reads the dropped x0 (and has the dropout epilogue)
+            return False
         return (self.cat_col == 0 and sp.E in (8, 16, 32, 64) and 0 < sp.S <= 40 and (sp.S * sp.E) % 32 == 0
                 and sp.S * sp.E <= self.in_ld[0] and self.rows_u.numel() * 4 < 0xFFFFFF00
                 and self.idx_inv is not None)
@@ -944,6 +988,17 @@ class CTREngine:
         e1.record()
         self.prof.append((label, e0, e1))
 
+    def _drop_args(self, layer):
+        """dl_gemm_s3_nt_drop / dl_dropout_apply's (keep_thr, inv, seed, layer, opt) of tensor
+        `layer` (include/dlamd.h "Dropout": 0 = the tower input, l + 1 = hidden layer l's output)."""
+        keep = self.drop[layer]
+        thr = min(int(math.floor(keep * 4294967296.0)), 4294967295)
+        inv = float(np.float32(1.0) / np.float32(keep))
+        return thr, inv, self.seed & 0xFFFFFFFFFFFFFFFF, layer, ptr(self.opt)
+
+    def _dropping(self, layer):
+        return bool(self.drop) and self.drop[layer] < 1.0
+
     def _forward(self, B, s, train=False):
         sp = self.spec
         L = self.layout
@@ -1023,6 +1078,10 @@ class CTREngine:
                     ptr(self.in_cont), ptr(self.in_vec), ptr(x0), ptr(self.fm_out), ptr(self.fm_sum),
                     ptr(self.err), s)
         nl = len(sp.hidden)
+        if train and self._dropping(0):
+            # input dropout on x0's deep_in columns (the bias "ones" column stays); predict never drops
+            self._c("drop_x0", "dl_dropout_apply", ptr(self.x0), B, self.D0, self.in_ld[0], *self._drop_args(0),
+                    None, s)
         if self.bf:
             # bf16 tower: x0 -> bf16, ReLU layers on bf16 MFMA (fp32 accumulate), the last layer's
             # output kept fp32 for the fp32 head / wide cross logit (config C5)
@@ -1063,6 +1122,11 @@ class CTREngine:
                             ptr(self.p_plane), FL.n_rows, self.p_plane.shape[1], ptr(self.in_cate), FL.cate_ld,
                             FL.deep_cate_offset, FL.zero_row0, sp.S, sp.E, ptr(self.WTp[0]), self.in_ld[0],
                             self.in_ld[0] * self.out_ld[0], ptr(self.h[0]), self.h_ld[0], 1, *bits, s)
+                elif train and self._dropping(l + 1):
+                    # ReLU + dropout in the epilogue; the bitmask holds (h > 0) & keep
+                    self._c("gemm_fwd_l%d" % l, "dl_gemm_s3_nt_drop", B, hdim, self.in_ld[l], ptr(x), self.in_ld[l],
+                            ptr(self.WTp[l]), self.in_ld[l], self.in_ld[l] * self.out_ld[l], ptr(self.h[l]),
+                            self.h_ld[l], 1, None, 0, *bits, *self._drop_args(l + 1), s)
                 else:
                     self._c("gemm_fwd_l%d" % l, "dl_gemm_s3_nt_bits", B, hdim, self.in_ld[l], ptr(x), self.in_ld[l],
                             ptr(self.WTp[l]), self.in_ld[l], self.in_ld[l] * self.out_ld[l], ptr(self.h[l]),
@@ -1172,6 +1236,11 @@ class CTREngine:
                 ptr(self.hist) if self.lazy else None, self.hist_len if self.lazy else 0, s)
         self._forward(B, s, train=True)
         nl = len(sp.hidden)
+        if self._dropping(nl):
+            # the head masked dh[-1] by h[-1] > 0, the combined bit of the dropped h[-1]: the
+            # 1/keep factor is what is missing (re-applying the regenerated mask changes nothing)
+            self._c("drop_dh", "dl_dropout_apply", ptr(self.dh[-1]), B, sp.hidden[-1], self.h_ld[-1],
+                    *self._drop_args(nl), None, s)
         dws = self._dw_splits(B, fixed="DLAMD_DW_SPLITS" in os.environ)
         if self.bf and not self.wdl:      # the wdl head writes its bf16 dY itself
             self._c("cast_dh", "dl_cast_bf16", ptr(self.dh[-1]), B, self.h_ld[-1], self.h_ld[-1], ptr(self.dhb[-1]),
@@ -1189,7 +1258,9 @@ class CTREngine:
             elif self.s3:   # dW = X^T dY (split-K slabs over the batch)
                 xin = self.x0 if l == 0 else self.h[l - 1]
                 i, o = self.in_ld[l], self.out_ld[l]
-                self._c("gemm_dw_l%d" % l, "dl_gemm_s3_tn", i, hdim, B, ptr(xin), i, ptr(self.dh[l]), self.h_ld[l],
+                # (a width that is no multiple of 4 is rounded up for the TN kernel: dh's pad columns
+                # are zero and stay so, so are their weight gradients)
+                self._c("gemm_dw_l%d" % l, "dl_gemm_s3_tn", i, _ru(hdim, 4), B, ptr(xin), i, ptr(self.dh[l]), self.h_ld[l],
                         ptr(self.w_slabs[l]), o, splits, stride, s)
             else:
                 xin = self.x0 if l == 0 else self.h[l - 1]
@@ -1208,7 +1279,11 @@ class CTREngine:
                             1, 0, s)
             elif self.s3:   # dX = dY W^T with ReluGrad
                 i, o = self.in_ld[l], self.out_ld[l]
-                if l > 0 and self.relu_bits:   # ReluGrad from the forward's sign bitmask
+                if l > 0 and self._dropping(l):   # ReluGrad and the keep bit from the combined bitmask, times 1/keep
+                    self._c("gemm_dx_l%d" % l, "dl_gemm_s3_nt_drop", B, sp.hidden[l - 1], o, ptr(self.dh[l]),
+                            self.h_ld[l], ptr(self.Wp[l]), o, i * o, ptr(self.dh[l - 1]), self.h_ld[l - 1], 3,
+                            None, 0, ptr(self.hbits[l - 1]), self.hbits_ld[l - 1], *self._drop_args(l), s)
+                elif l > 0 and self.relu_bits:   # ReluGrad from the forward's sign bitmask
                     self._c("gemm_dx_l%d" % l, "dl_gemm_s3_nt_bits", B, sp.hidden[l - 1], o, ptr(self.dh[l]),
                             self.h_ld[l], ptr(self.Wp[l]), o, i * o, ptr(self.dh[l - 1]), self.h_ld[l - 1], 3,
                             None, 0, ptr(self.hbits[l - 1]), self.hbits_ld[l - 1], s)
@@ -1219,6 +1294,9 @@ class CTREngine:
                 else:
                     self._c("gemm_dx_l0", "dl_gemm_s3_nt", B, self.dx_cols, o, ptr(self.dh[0]), self.h_ld[0],
                             ptr(self.Wp[0]), o, i * o, ptr(self.dx0), self.dx_ld, 0, None, 0, s)
+                    if self._dropping(0):   # the input dropout's mask on the embedding columns' gradient
+                        self._c("drop_dx0", "dl_dropout_apply", ptr(self.dx0), B, self.dx_cols, self.dx_ld,
+                                *self._drop_args(0), None, s)
             else:
                 self._c("transpose_l%d" % l, "dl_transpose_f32", ptr(self.W[l]), self.in_ld[l], self.out_ld[l],
                         self.out_ld[l], ptr(self.Wt), self.in_ld[l], s)

@@ -44,6 +44,9 @@ def _spec_from_args(model, args):
     kw.update(S=int(args.cate_field_size), C=int(getattr(args, "cont_field_size", 0) or 0))
     if FAMILIES[model]["multi"]:   # slot ranges within the multi block (my_utils.feat_size)
         kw.update(multi_ranges=[list(r) for r in args.multi_feats_range])
+    keep = getattr(args, "dropout_keep_deep", None)
+    if keep is not None:   # local_run.py:40; the engine drops only where a keep is below 1
+        kw.update(dropout_keep_deep=[float(k) for k in keep])
     return ModelSpec(model, **kw)
 
 

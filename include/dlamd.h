@@ -381,6 +381,34 @@ int dl_gemm_s3_nt_gather_tab(int32_t M, int32_t N, int32_t K, const float* A, in
                              uint16_t* bits, int32_t ldbits, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Dropout of the deep tower (the reference's dropout_keep_deep: tf.nn.dropout after the tower
+ * input and after every ReLU layer, deepfm_pipeline.py:148-153).  The mask is a pure function,
+ * never stored:
+ *   keep(seed, step, layer, row, col) = word (col & 3) of
+ *       Philox-4x32-10(counter = (row, col >> 2, layer, step), key = (seed & 0xffffffff, seed >> 32))
+ *       < keep_thr,       keep_thr = min(floor(keep * 2^32), 2^32 - 1)
+ * (the counter's and the output's words in the order x, y, z, w of Salmon et al.'s definition;
+ * all fields unsigned 32-bit).  One Philox call yields the four consecutive columns
+ * 4 (col >> 2) .. + 3 of one row: what one lane of the s3 NT epilogue stores.  row and col are
+ * the element's indices in the tensor as the engine lays it out (x0's columns in its internal
+ * order); layer 0 is the tower input, layer i + 1 the output of hidden layer i; step is
+ * (uint32) opt[7], read on the device, so a replayed graph draws a new mask every step.  A kept
+ * element is multiplied by inv = float32(1) / float32(keep) (computed by the caller, one f32
+ * multiply), a dropped one is 0.
+ * dl_gemm_s3_nt_drop: dl_gemm_s3_nt_bits, epi 1 or 3 only.
+ *   epi 1: v = relu(acc); C = keep ? v * inv : 0; bitmask bit = (v > 0) & keep (bits may be
+ *          NULL; bits of columns >= N in the last halfword are 0).
+ *   epi 3: C = bit ? C * inv : 0 — reads the combined mask epi 1 wrote, no RNG.
+ * dl_dropout_apply: x[M][ld] (columns [0, N) only) = keep ? x * inv : 0 in place; mask_out (may
+ *   be NULL; uint8 [M][N]) receives the keep bits; x == NULL: only mask_out is written. */
+int dl_gemm_s3_nt_drop(int32_t M, int32_t N, int32_t K, const float* A, int32_t lda, const uint16_t* B,
+                       int32_t ldb, int64_t b_plane, float* C, int32_t ldc, int32_t epi, const float* mask,
+                       int32_t ldm, uint16_t* bits, int32_t ldbits, uint32_t keep_thr, float inv, uint64_t seed,
+                       int32_t layer, const float* opt, void* stream);
+int dl_dropout_apply(float* x, int32_t M, int32_t N, int32_t ld, uint32_t keep_thr, float inv, uint64_t seed,
+                     int32_t layer, const float* opt, uint8_t* mask_out, void* stream);
+
+/* ------------------------------------------------------------------------
  * Output layer + sigmoid + eps-log-loss, forward and backward fused
  * (deepfm_pipeline.py:157-183, dnn_pipeline.py:119-131):
  * z = [fm_out(F+E) | h(H)] . w + w[F+E+H];  p = sigmoid(z);

@@ -47,7 +47,13 @@ class PoolDesc(C.Structure):
     ]
 
 
+class FmDrop(C.Structure):
+    """Mirror of ``dl_fm_drop`` (include/dlamd.h "Dropout")."""
+    _fields_ = [("fm_keep", C.c_void_p), ("inv1", C.c_float), ("inv2", C.c_float)]
+
+
 # include/dlamd.h constants
+DROP_LAYER_FM1, DROP_LAYER_FM2 = 1 << 16, (1 << 16) + 1
 OPT_LEN, OPT_STATUS, OPT_SKIP, OPT_BAD_STEP, OPT_BAD_COUNT, OPT_SEQ, OPT_BAD_RANKS = 32, 16, 17, 18, 19, 20, 21
 STATUS_BAD_ID, STATUS_LAG, STATUS_INDEX, STATUS_OVERFLOW, STATUS_DESYNC = 1, 2, 4, 8, 16
 REC_FIRST, REC_SPARSE_ADAM, REC_PLANE_SLOTS = 1, 2, 4
@@ -77,6 +83,7 @@ SIGNATURES = {
     "dl_device_sync": (I32, []),
     "dl_embed_fwd": (I32, [LP, P, P, P, P, P, P, P, P, P, P]),
     "dl_embed_bwd": (I32, [LP, P, P, P, P, P, P, P, P, P, P, P, I32, P]),
+    "dl_embed_bwd_fmdrop": (I32, [LP, P, P, P, P, P, P, P, P, P, P, P, I32, P, P]),
     "dl_embed_bwd_grid": (I32, [LP]),
     "dl_embed_cont_reduce": (I32, [LP, P, I32, P, P, P, P]),
     "dl_embed_fwd_indexed": (I32, [LP, P, P, P, I32, P, P, P, P, P, P]),
@@ -93,13 +100,16 @@ SIGNATURES = {
     "dl_slab_sum": (I32, [P, I32, I64, I64, P, P]),
     "dl_keys_to_local": (I32, [P, P, I64, P, P]),
     "dl_embed_cont_bwd": (I32, [LP, P, P, P, P, P, P, I32, P]),
+    "dl_embed_cont_bwd_fmdrop": (I32, [LP, P, P, P, P, P, P, I32, P, P]),
     "dl_index_workspace_bytes": (I64, [I64]),
     "dl_index_build": (I32, [LP, P, I32, I32, P, I64, P, P, P, P, P, P, P, P, P]),
     "dl_index_build_pair": (I32, [LP, P, LP, P, P, I64, P, P, P, P, P, P, P, P, P, P, P, P, P]),
     "dl_embed_bwd_sorted": (I32, [LP, P, P, P, P, P, P, I32, I64, P, P, P, P, P, P, P, I32, P, P]),
+    "dl_embed_bwd_sorted_fmdrop": (I32, [LP, P, P, P, P, P, P, I32, I64, P, P, P, P, P, P, P, I32, P, P, P]),
     "dl_pool_fwd": (I32, [LP, P, P, P, I32, P, P, I32, I32, P, P, P, P, P, P]),
     "dl_pool_fwd_indexed": (I32, [LP, P, P, P, I32, P, P, I32, I32, P, P, P, P, P]),
     "dl_pool_bwd": (I32, [LP, P, I32, P, P, I32, I32, P, P, P, P, P, I32, P, P, P, P, P, P]),
+    "dl_pool_bwd_fmdrop": (I32, [LP, P, I32, P, P, I32, I32, P, P, P, P, P, I32, P, P, P, P, P, P, P]),
     "dl_pool_fwd_weighted": (I32, [LP, P, P, I32, P, I32, P, P, I32, P, P, P, P]),
     "dl_pool_bwd_weighted": (I32, [LP, P, I32, P, I32, P, P, I32, P, I32, P, P, P, P]),
     "dl_gemm_f32": (I32, [I32, I32, I32, I32, I32, P, I32, P, I32, P, I32, I32, P, I32, I32, I64, P]),
@@ -119,6 +129,8 @@ SIGNATURES = {
                                        P, I32, P]),
     "dl_gemm_s3_tn": (I32, [I32, I32, I32, P, I32, P, I32, P, I32, I32, I64, P]),
     "dl_head_fwd_bwd": (I32, [I32, I32, I32, P, I32, P, I32, P, P, F, F, P, P, P, P, P, I32, P]),
+    "dl_head_fwd_bwd_fmdrop": (I32, [I32, I32, I32, P, I32, P, I32, P, P, F, F, P, P, P, P, P, I32, I32, U32, F, U32, F,
+                                     U64, P, P, P]),
     "dl_head_grid": (I32, [I32]),
     "dl_wdl_head_grid": (I32, [I32]),
     "dl_wdl_head_fwd_bwd": (I32, [I32, I32, I32, P, I32, P, I32, P, P, I64, P, F, F, P, P, P, P, P, P, P, I32, P, P]),
@@ -148,6 +160,8 @@ SIGNATURES = {
     "dl_embed_fwd_staged": (I32, [LP, P, P, P, I32, P, P, P, P, P, P]),
     "dl_rec_bwd_adam": (I32, [LP, P, I32, I32, I32, P, P, P, P, P, P, P, I32, I64, P, P, P, P, P, P, P, I32, P,
                               P, P, I64, P]),
+    "dl_rec_bwd_adam_fmdrop": (I32, [LP, P, I32, I32, I32, P, P, P, P, P, P, P, I32, I64, P, P, P, P, P, P, P, I32, P,
+                                     P, P, I64, P, P]),
     "dl_rec_bwd_workspace_bytes": (I64, [I64, I32]),
     "dl_rec_apply_rows": (I32, [P, I32, I32, I32, I64, I64, P, P, P, I32, P, P]),
     "dl_sort_unique": (I32, [P, I64, I32, P, I64, P, P, P, P, P, P, P]),

@@ -375,11 +375,12 @@ struct EmbBwdArgs {
   float* g_first;
   uint8_t* touched;
   float* cont_slab;
+  FmDrop drop;   // the DROP instantiations (segment.h "FM-part dropout")
 };
 
 constexpr int kMaxHotCont = 32;  // cont fields kept in registers on the backward
 
-template <int E, bool CONT_ONLY>
+template <int E, bool CONT_ONLY, bool DROP = false>
 __global__ __launch_bounds__(256) void embed_bwd_kernel(EmbBwdArgs a) {
   constexpr int RPI = 64 / E;  // rows per wave instruction (lane = dim)
   constexpr int NCP = (kMaxHotCont + RPI - 1) / RPI;
@@ -404,7 +405,10 @@ __global__ __launch_bounds__(256) void embed_bwd_kernel(EmbBwdArgs a) {
     if (L.use_fm) {
       const float dzb = a.dz[b];
       const float* cb = a.cont + (int64_t)b * L.cont_fields;
-      const float dsec = dzb * a.w_head[F + d];
+      ulonglong2 kw = make_ulonglong2(0ull, 0ull);
+      if constexpr (DROP) kw = fm_keep_words(a.drop, b);
+      const float dsec = DROP ? fm_dfm(fm_keep_bit(kw, F + d), dzb, a.w_head[F + d], a.drop.inv2)
+                              : dzb * a.w_head[F + d];
       const float sd = a.fm_sum[(int64_t)b * E + d];
       // hot cont-field rows: register accumulation
 #pragma unroll
@@ -430,12 +434,13 @@ __global__ __launch_bounds__(256) void embed_bwd_kernel(EmbBwdArgs a) {
         }
       }
       for (int f = lane; f < Fs; f += 64) {
+        const float d1 = DROP ? fm_dfm(fm_keep_bit(kw, f), dzb, a.w_head[f], a.drop.inv1) : dzb * a.w_head[f];
         if (f < Cf) {
-          g1c += dzb * a.w_head[f] * cb[f];
+          g1c += d1 * cb[f];
         } else if (!CONT_ONLY) {
           const int64_t row = ids[f - Cf] + L.fm_cate_offset;
           if (row < L.n_rows && row_ok(row, L.zero_row0)) {
-            atomicAdd(a.g_first + row, dzb * a.w_head[f]);
+            atomicAdd(a.g_first + row, d1);
             a.touched[row] = 1;
           }
         }
@@ -476,7 +481,7 @@ __global__ __launch_bounds__(256) void embed_bwd_kernel(EmbBwdArgs a) {
 // rest): E / 4 lanes per sample, one float4 of the dims each, every field of the sample in
 // the lane's registers, so a wave covers 64 / (E / 4) samples per load round trip instead
 // of one.  Per-element terms as embed_bwd_kernel's; block partials to cont_slab[block].
-template <int E, int NC>
+template <int E, int NC, bool DROP = false>
 __global__ __launch_bounds__(256) void cont_bwd_kernel(EmbBwdArgs a) {
   constexpr int QPR = E / 4, SPW = 64 / QPR;
   const dl_emb_layout& L = a.L;
@@ -516,11 +521,13 @@ __global__ __launch_bounds__(256) void cont_bwd_kernel(EmbBwdArgs a) {
        b0 < L.batch; b0 += kIt * stride) {
     float dzv[kIt], cv[kIt][NC];
     float4 sdv[kIt];
+    ulonglong2 kwv[DROP ? kIt : 1];
 #pragma unroll
     for (int i = 0; i < kIt; ++i) {
       const int b = b0 + i * stride;
       const int bc = b < L.batch ? b : b0;
       dzv[i] = a.dz[bc];
+      if constexpr (DROP) kwv[i] = fm_keep_words(a.drop, bc);
       sdv[i] = *reinterpret_cast<const float4*>(a.fm_sum + (int64_t)bc * E + 4 * q);
 #pragma unroll
       for (int f = 0; f < NC; ++f) cv[i][f] = f < Cf ? a.cont[(int64_t)bc * Cf + f] : 0.f;
@@ -530,7 +537,13 @@ __global__ __launch_bounds__(256) void cont_bwd_kernel(EmbBwdArgs a) {
       if (b0 + i * stride >= L.batch) break;
       const float dzb = dzv[i];
       const float4 sd = sdv[i];
-      const float d0 = dzb * w0, d1 = dzb * w1, d2 = dzb * w2, d3 = dzb * w3;
+      float d0, d1, d2, d3;
+      if constexpr (DROP) {
+        const float4 dd = fm_dfm4(fm_keep_bits4(kwv[i], F + 4 * q), dzb, make_float4(w0, w1, w2, w3), a.drop.inv2);
+        d0 = dd.x; d1 = dd.y; d2 = dd.z; d3 = dd.w;
+      } else {
+        d0 = dzb * w0; d1 = dzb * w1; d2 = dzb * w2; d3 = dzb * w3;
+      }
 #pragma unroll
       for (int f = 0; f < NC; ++f) {
         if (f < Cf) {
@@ -552,7 +565,11 @@ __global__ __launch_bounds__(256) void cont_bwd_kernel(EmbBwdArgs a) {
 #pragma unroll
         for (int t = 1; t < QPR; ++t)
           if (q == t) cf = cv[i][QPR * j + t];
-        if (f < Cf) g1[j] += dzb * wf[j] * cf;
+        if constexpr (DROP) {
+          if (f < Cf) g1[j] += fm_dfm(fm_keep_bit(kwv[i], f), dzb, wf[j], a.drop.inv1) * cf;
+        } else {
+          if (f < Cf) g1[j] += dzb * wf[j] * cf;
+        }
       }
     }
   }
@@ -928,9 +945,10 @@ struct PoolBwdArgs {
   uint8_t* touched;
   const float* vals;       // weighted mode (see PoolArgs)
   int vals_ld;
+  FmDrop drop;             // the DROP instantiation (segment.h "FM-part dropout")
 };
 
-template <int E, bool WT = false>
+template <int E, bool WT = false, bool DROP = false>
 __global__ __launch_bounds__(256) void pool_bwd_kernel(PoolBwdArgs a) {
   constexpr int RPI = 64 / E;
   const dl_emb_layout& L = a.L;
@@ -942,13 +960,20 @@ __global__ __launch_bounds__(256) void pool_bwd_kernel(PoolBwdArgs a) {
   for (int b = wave; b < L.batch; b += nwaves) {
     const int64_t* ids = a.ids + (int64_t)b * L.cate_ld + a.ids_col;
     const float dzb = L.use_fm ? a.dz[b] : 0.f;
-    const float dsec = L.use_fm ? dzb * a.w_head[F + d] : 0.f;
+    ulonglong2 kw = make_ulonglong2(0ull, 0ull);
+    if constexpr (DROP) kw = fm_keep_words(a.drop, b);
+    const float dsec = !L.use_fm ? 0.f
+                       : DROP    ? fm_dfm(fm_keep_bit(kw, F + d), dzb, a.w_head[F + d], a.drop.inv2)
+                                 : dzb * a.w_head[F + d];
     const float sd = L.use_fm ? a.fm_sum[(int64_t)b * E + d] : 0.f;
     for (int m = 0; m < a.n_slots; ++m) {
       const int s0 = a.slot_start[m], s1 = a.slot_end[m];
       const float pooled = a.x0[(int64_t)b * L.x0_ld + L.x0_pool_col + m * E + d];
       float dp = a.dx0[(int64_t)b * L.dx0_ld + a.dx0_pool_col + m * E + d];
-      if (L.use_fm) dp += dsec * (sd - pooled);
+      if (L.use_fm) {
+        if constexpr (DROP) dp = fmaf(dsec, sd - pooled, dp);   // as rec.hip pool_grad_kernel forms it
+        else dp += dsec * (sd - pooled);
+      }
       const float c = a.cnt_emb[(int64_t)b * a.n_slots + m];
       const float gv = c > 0.f ? dp / c : 0.f;   // div_no_nan gradient
       for (int l0 = s0; l0 < s1; l0 += RPI) {
@@ -963,7 +988,9 @@ __global__ __launch_bounds__(256) void pool_bwd_kernel(PoolBwdArgs a) {
       }
       if (L.use_fm && a.g_first) {
         const float c1 = a.cnt_first[(int64_t)b * a.n_slots + m];
-        const float g1 = c1 > 0.f ? dzb * a.w_head[a.fm_col + m] / c1 : 0.f;
+        const float g1 = c1 <= 0.f ? 0.f
+                         : DROP    ? fm_dfm(fm_keep_bit(kw, a.fm_col + m), dzb, a.w_head[a.fm_col + m], a.drop.inv1) / c1
+                                   : dzb * a.w_head[a.fm_col + m] / c1;
         for (int l = s0 + lane; l < s1; l += 64) {
           const int64_t row = ids[l];
           if (row < L.n_rows && row_ok(row, L.zero_row0)) {
@@ -1161,21 +1188,49 @@ static int launch_embed_fwd(const dl_emb_layout* L, const EmbArgs& a, void* stre
 
 extern "C" int dl_embed_bwd_grid(const dl_emb_layout* L) { return emb_grid(L->batch) < 1024 ? emb_grid(L->batch) : 1024; }
 
-extern "C" int dl_embed_bwd(const dl_emb_layout* L, const float* table, const int64_t* cate,
-                            const float* cont, const float* dz, const float* w_head,
-                            const float* fm_sum, const float* dx0, float* g_table, float* g_first,
-                            uint8_t* touched, float* cont_slab, int32_t cont_slab_blocks,
-                            void* stream) {
+// The *_fmdrop entry points are their plain namesakes with the FM-part dropout factor
+// (segment.h "FM-part dropout"); `drop` NULL: the plain kernels.
+static int embed_bwd_impl(const dl_emb_layout* L, const float* table, const int64_t* cate,
+                          const float* cont, const float* dz, const float* w_head,
+                          const float* fm_sum, const float* dx0, float* g_table, float* g_first,
+                          uint8_t* touched, float* cont_slab, int32_t cont_slab_blocks,
+                          const dl_fm_drop* drop, void* stream) {
   if (int rc = check_layout(L)) return rc;
+  if (int rc = fm_drop_check(L, drop)) return rc;
   if (L->batch == 0) return 0;
   const int grid = dl_embed_bwd_grid(L);
   const bool hot = L->use_fm && L->fm_cont && L->cont_fields > 0;
   DL_CHECK_ARG(!hot || (cont_slab && cont_slab_blocks >= grid), "cont_slab needs %d blocks", grid);
   DL_CHECK_ARG(!L->use_fm || (dz && w_head && fm_sum && g_first), "FM backward inputs required");
   EmbBwdArgs a{*L, table, cate, cont, dz, w_head, fm_sum, dx0, g_table, g_first, touched, cont_slab};
+  if (drop) {
+    a.drop = fm_drop_of(drop);
+    DL_DISPATCH_E(L->emb_dim, hipLaunchKernelGGL((embed_bwd_kernel<kE, false, true>), dim3(grid), dim3(256), 0,
+                                                 as_stream(stream), a));
+    DL_RETURN_LAUNCH("dl_embed_bwd_fmdrop");
+  }
   DL_DISPATCH_E(L->emb_dim, hipLaunchKernelGGL((embed_bwd_kernel<kE, false>), dim3(grid), dim3(256), 0,
                                                as_stream(stream), a));
   DL_RETURN_LAUNCH("dl_embed_bwd");
+}
+
+extern "C" int dl_embed_bwd(const dl_emb_layout* L, const float* table, const int64_t* cate,
+                            const float* cont, const float* dz, const float* w_head,
+                            const float* fm_sum, const float* dx0, float* g_table, float* g_first,
+                            uint8_t* touched, float* cont_slab, int32_t cont_slab_blocks,
+                            void* stream) {
+  return embed_bwd_impl(L, table, cate, cont, dz, w_head, fm_sum, dx0, g_table, g_first, touched, cont_slab,
+                        cont_slab_blocks, nullptr, stream);
+}
+
+extern "C" int dl_embed_bwd_fmdrop(const dl_emb_layout* L, const float* table, const int64_t* cate,
+                                   const float* cont, const float* dz, const float* w_head,
+                                   const float* fm_sum, const float* dx0, float* g_table, float* g_first,
+                                   uint8_t* touched, float* cont_slab, int32_t cont_slab_blocks,
+                                   const dl_fm_drop* drop, void* stream) {
+  DL_CHECK_ARG(drop, "drop is NULL");
+  return embed_bwd_impl(L, table, cate, cont, dz, w_head, fm_sum, dx0, g_table, g_first, touched, cont_slab,
+                        cont_slab_blocks, drop, stream);
 }
 
 extern "C" int dl_embed_cont_reduce(const dl_emb_layout* L, const float* cont_slab, int32_t blocks,
@@ -1245,19 +1300,47 @@ extern "C" int dl_pool_fwd_staged(const dl_emb_layout* L, const float* mst, cons
   DL_RETURN_LAUNCH("dl_pool_fwd_staged");
 }
 
+static int pool_bwd_impl(const dl_emb_layout* L, const int64_t* ids, int32_t ids_col,
+                         const int32_t* slot_start, const int32_t* slot_end, int32_t n_slots,
+                         int32_t fm_col, const float* x0, const float* fm_sum, const float* dz,
+                         const float* w_head, const float* dx0, int32_t dx0_pool_col,
+                         const float* cnt_emb, const float* cnt_first, float* g_table,
+                         float* g_first, uint8_t* touched, const dl_fm_drop* drop, void* stream) {
+  if (int rc = check_layout(L)) return rc;
+  if (int rc = fm_drop_check(L, drop)) return rc;
+  if (L->batch == 0 || n_slots == 0) return 0;
+  PoolBwdArgs a{*L, ids, ids_col, slot_start, slot_end, n_slots, fm_col, x0, fm_sum, dz, w_head,
+                dx0, dx0_pool_col, cnt_emb, cnt_first, g_table, g_first, touched, nullptr, 0};
+  if (drop) {
+    a.drop = fm_drop_of(drop);
+    DL_DISPATCH_E(L->emb_dim, hipLaunchKernelGGL((pool_bwd_kernel<kE, false, true>), dim3(emb_grid(L->batch)),
+                                                 dim3(256), 0, as_stream(stream), a));
+    DL_RETURN_LAUNCH("dl_pool_bwd_fmdrop");
+  }
+  DL_DISPATCH_E(L->emb_dim, hipLaunchKernelGGL(pool_bwd_kernel<kE>, dim3(emb_grid(L->batch)),
+                                               dim3(256), 0, as_stream(stream), a));
+  DL_RETURN_LAUNCH("dl_pool_bwd");
+}
+
 extern "C" int dl_pool_bwd(const dl_emb_layout* L, const int64_t* ids, int32_t ids_col,
                            const int32_t* slot_start, const int32_t* slot_end, int32_t n_slots,
                            int32_t fm_col, const float* x0, const float* fm_sum, const float* dz,
                            const float* w_head, const float* dx0, int32_t dx0_pool_col,
                            const float* cnt_emb, const float* cnt_first, float* g_table,
                            float* g_first, uint8_t* touched, void* stream) {
-  if (int rc = check_layout(L)) return rc;
-  if (L->batch == 0 || n_slots == 0) return 0;
-  PoolBwdArgs a{*L, ids, ids_col, slot_start, slot_end, n_slots, fm_col, x0, fm_sum, dz, w_head,
-                dx0, dx0_pool_col, cnt_emb, cnt_first, g_table, g_first, touched, nullptr, 0};
-  DL_DISPATCH_E(L->emb_dim, hipLaunchKernelGGL(pool_bwd_kernel<kE>, dim3(emb_grid(L->batch)),
-                                               dim3(256), 0, as_stream(stream), a));
-  DL_RETURN_LAUNCH("dl_pool_bwd");
+  return pool_bwd_impl(L, ids, ids_col, slot_start, slot_end, n_slots, fm_col, x0, fm_sum, dz, w_head, dx0,
+                       dx0_pool_col, cnt_emb, cnt_first, g_table, g_first, touched, nullptr, stream);
+}
+
+extern "C" int dl_pool_bwd_fmdrop(const dl_emb_layout* L, const int64_t* ids, int32_t ids_col,
+                                  const int32_t* slot_start, const int32_t* slot_end, int32_t n_slots,
+                                  int32_t fm_col, const float* x0, const float* fm_sum, const float* dz,
+                                  const float* w_head, const float* dx0, int32_t dx0_pool_col,
+                                  const float* cnt_emb, const float* cnt_first, float* g_table,
+                                  float* g_first, uint8_t* touched, const dl_fm_drop* drop, void* stream) {
+  DL_CHECK_ARG(drop, "drop is NULL");
+  return pool_bwd_impl(L, ids, ids_col, slot_start, slot_end, n_slots, fm_col, x0, fm_sum, dz, w_head, dx0,
+                       dx0_pool_col, cnt_emb, cnt_first, g_table, g_first, touched, drop, stream);
 }
 
 extern "C" int dl_pool_fwd_weighted(const dl_emb_layout* L, const float* table, const int64_t* ids,
@@ -1324,6 +1407,7 @@ struct BwdSortedArgs {
   int compact;
   const int32_t* upos;     // compact: the slot of unique row u in rows_u / g_out (sharded exchange
                            // blocks, dl_shard_route; -1 = no slot), NULL = u itself
+  FmDrop drop;             // the DROP instantiations (segment.h "FM-part dropout")
 };
 
 
@@ -1353,7 +1437,7 @@ __device__ __forceinline__ void embed_bwd_sorted_row(const BwdSortedArgs& a, lon
 
 // float4 lanes (E/4 per unique row, as rec_bwd_adam_kernel): a wave keeps 64/(E/4)
 // rows' segment walks in flight; sums are bit-identical to the per-dim form.
-template <int E>
+template <int E, bool DROP = false>
 __global__ __launch_bounds__(256) void embed_bwd_sorted_kernel(BwdSortedArgs a) {
   constexpr int LPR = E / 4;
   const dl_emb_layout& L = a.L;
@@ -1368,16 +1452,17 @@ __global__ __launch_bounds__(256) void embed_bwd_sorted_kernel(BwdSortedArgs a) 
   const int nu = clamp_uniq(a.n_uniq, nrefs);
   const float* ws = a.w_head + F + 4 * q;   // not 16-B aligned
   const float4 wsec = L.use_fm ? make_float4(ws[0], ws[1], ws[2], ws[3]) : make_float4(0.f, 0.f, 0.f, 0.f);
-  const SegGradIn sg{L, a.seg_off, a.refs, a.dz, a.w_head, a.fm_sum, a.dx0};
+  SegGradIn sg{L, a.seg_off, a.refs, a.dz, a.w_head, a.fm_sum, a.dx0};
+  if constexpr (DROP) sg.drop = a.drop;
   for (long long u = group0; u < nu; u += ngroups) {
     const SegRange cr = seg_range(sg, u, nu, nrefs);
     if (cr.e1 - cr.e0 > kSegLong) continue;   // a hot row: embed_bwd_long_kernel
-    const SegGrad4 sgr = segment_grad4_range<E>(sg, cr.e0, cr.e1, -2, q, nrefs, wsec);
+    const SegGrad4 sgr = segment_grad4_range<E, DROP>(sg, cr.e0, cr.e1, -2, q, nrefs, wsec);
     embed_bwd_sorted_row<E>(a, u, q, sgr);
   }
 }
 
-template <int E>
+template <int E, bool DROP = false>
 __global__ __launch_bounds__(256) void embed_bwd_long_kernel(BwdSortedArgs a) {
   __shared__ SegLongLds sh;
   const dl_emb_layout& L = a.L;
@@ -1389,19 +1474,22 @@ __global__ __launch_bounds__(256) void embed_bwd_long_kernel(BwdSortedArgs a) {
   const int nu = clamp_uniq(a.n_uniq, nrefs);
   const float* ws = a.w_head + F + 4 * q;
   const float4 wsec = L.use_fm ? make_float4(ws[0], ws[1], ws[2], ws[3]) : make_float4(0.f, 0.f, 0.f, 0.f);
-  const SegGradIn sg{L, a.seg_off, a.refs, a.dz, a.w_head, a.fm_sum, a.dx0};
-  for_long_segments<E>(sg, nu, nrefs, wsec, sh, [&](long long u, const SegGrad4& s) { embed_bwd_sorted_row<E>(a, u, q, s); });
+  SegGradIn sg{L, a.seg_off, a.refs, a.dz, a.w_head, a.fm_sum, a.dx0};
+  if constexpr (DROP) sg.drop = a.drop;
+  for_long_segments<E, DROP>(sg, nu, nrefs, wsec, sh,
+                             [&](long long u, const SegGrad4& s) { embed_bwd_sorted_row<E>(a, u, q, s); });
 }
 
 }  // namespace dl
 
-extern "C" int dl_embed_bwd_sorted(const dl_emb_layout* L, const float* table, const float* rows_u,
-                                   const uint32_t* uniq_keys, const int32_t* seg_off, const int32_t* n_uniq,
-                                   const int32_t* sorted_refs, int32_t world, int64_t max_uniq,
-                                   const float* dz, const float* w_head, const float* fm_sum,
-                                   const float* dx0, float* g_out, float* g1_out, uint8_t* touched,
-                                   int32_t compact, const int32_t* upos, void* stream) {
+static int embed_bwd_sorted_impl(const dl_emb_layout* L, const float* table, const float* rows_u,
+                                 const uint32_t* uniq_keys, const int32_t* seg_off, const int32_t* n_uniq,
+                                 const int32_t* sorted_refs, int32_t world, int64_t max_uniq,
+                                 const float* dz, const float* w_head, const float* fm_sum,
+                                 const float* dx0, float* g_out, float* g1_out, uint8_t* touched,
+                                 int32_t compact, const int32_t* upos, const dl_fm_drop* drop, void* stream) {
   if (int rc = check_layout(L)) return rc;
+  if (int rc = fm_drop_check(L, drop)) return rc;
   DL_CHECK_ARG(uniq_keys && seg_off && n_uniq && sorted_refs && dx0 && g_out, "NULL argument");
   DL_CHECK_ARG(table || rows_u, "need the table or the gathered rows");
   DL_CHECK_ARG(compact || touched, "dense output needs the touched flags");
@@ -1412,6 +1500,14 @@ extern "C" int dl_embed_bwd_sorted(const dl_emb_layout* L, const float* table, c
   if (blocks > 8192) blocks = 8192;
   BwdSortedArgs a{*L, table, rows_u, uniq_keys, seg_off, n_uniq, sorted_refs, world, dz, w_head, fm_sum, dx0,
                   g_out, g1_out, touched, compact, compact ? upos : nullptr};
+  if (drop) {
+    a.drop = fm_drop_of(drop);
+    DL_DISPATCH_E(L->emb_dim, {
+      hipLaunchKernelGGL((embed_bwd_sorted_kernel<kE, true>), dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), a);
+      hipLaunchKernelGGL((embed_bwd_long_kernel<kE, true>), dim3(1024), dim3(256), 0, as_stream(stream), a);
+    });
+    DL_RETURN_LAUNCH("dl_embed_bwd_sorted_fmdrop");
+  }
   DL_DISPATCH_E(L->emb_dim, {
     hipLaunchKernelGGL(embed_bwd_sorted_kernel<kE>, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), a);
     hipLaunchKernelGGL(embed_bwd_long_kernel<kE>, dim3(1024), dim3(256), 0, as_stream(stream), a);
@@ -1419,16 +1515,49 @@ extern "C" int dl_embed_bwd_sorted(const dl_emb_layout* L, const float* table, c
   DL_RETURN_LAUNCH("dl_embed_bwd_sorted");
 }
 
-extern "C" int dl_embed_cont_bwd(const dl_emb_layout* L, const float* table, const float* cont,
-                                 const float* dz, const float* w_head, const float* fm_sum, float* cont_slab,
-                                 int32_t cont_slab_blocks, void* stream) {
+extern "C" int dl_embed_bwd_sorted(const dl_emb_layout* L, const float* table, const float* rows_u,
+                                   const uint32_t* uniq_keys, const int32_t* seg_off, const int32_t* n_uniq,
+                                   const int32_t* sorted_refs, int32_t world, int64_t max_uniq,
+                                   const float* dz, const float* w_head, const float* fm_sum,
+                                   const float* dx0, float* g_out, float* g1_out, uint8_t* touched,
+                                   int32_t compact, const int32_t* upos, void* stream) {
+  return embed_bwd_sorted_impl(L, table, rows_u, uniq_keys, seg_off, n_uniq, sorted_refs, world, max_uniq, dz, w_head,
+                               fm_sum, dx0, g_out, g1_out, touched, compact, upos, nullptr, stream);
+}
+
+extern "C" int dl_embed_bwd_sorted_fmdrop(const dl_emb_layout* L, const float* table, const float* rows_u,
+                                          const uint32_t* uniq_keys, const int32_t* seg_off, const int32_t* n_uniq,
+                                          const int32_t* sorted_refs, int32_t world, int64_t max_uniq,
+                                          const float* dz, const float* w_head, const float* fm_sum,
+                                          const float* dx0, float* g_out, float* g1_out, uint8_t* touched,
+                                          int32_t compact, const int32_t* upos, const dl_fm_drop* drop,
+                                          void* stream) {
+  DL_CHECK_ARG(drop, "drop is NULL");
+  return embed_bwd_sorted_impl(L, table, rows_u, uniq_keys, seg_off, n_uniq, sorted_refs, world, max_uniq, dz, w_head,
+                               fm_sum, dx0, g_out, g1_out, touched, compact, upos, drop, stream);
+}
+
+static int embed_cont_bwd_impl(const dl_emb_layout* L, const float* table, const float* cont,
+                               const float* dz, const float* w_head, const float* fm_sum, float* cont_slab,
+                               int32_t cont_slab_blocks, const dl_fm_drop* drop, void* stream) {
   if (int rc = check_layout(L)) return rc;
+  if (int rc = fm_drop_check(L, drop)) return rc;
   if (L->batch == 0 || !(L->use_fm && L->fm_cont && L->cont_fields > 0)) return 0;
   // blocks: cont_slab_blocks, at most dl_embed_bwd_grid (blocks past the samples' share write
   // zero partials, so a caller may pass just the blocks that hold samples: same partials)
   const int grid = min(dl_embed_bwd_grid(L), (int)cont_slab_blocks);
   DL_CHECK_ARG(cont_slab && cont_slab_blocks >= 1, "cont_slab needs at least one block");
   EmbBwdArgs a{*L, table, nullptr, cont, dz, w_head, fm_sum, nullptr, nullptr, nullptr, nullptr, cont_slab};
+  if (drop) {
+    a.drop = fm_drop_of(drop);
+    DL_DISPATCH_E(L->emb_dim, {
+      if (L->cont_fields <= 16)
+        hipLaunchKernelGGL((cont_bwd_kernel<kE, 16, true>), dim3(grid), dim3(256), 0, as_stream(stream), a);
+      else
+        hipLaunchKernelGGL((cont_bwd_kernel<kE, kMaxHotCont, true>), dim3(grid), dim3(256), 0, as_stream(stream), a);
+    });
+    DL_RETURN_LAUNCH("dl_embed_cont_bwd_fmdrop");
+  }
   DL_DISPATCH_E(L->emb_dim, {
     if (L->cont_fields <= 16)
       hipLaunchKernelGGL((cont_bwd_kernel<kE, 16>), dim3(grid), dim3(256), 0, as_stream(stream), a);
@@ -1436,4 +1565,17 @@ extern "C" int dl_embed_cont_bwd(const dl_emb_layout* L, const float* table, con
       hipLaunchKernelGGL((cont_bwd_kernel<kE, kMaxHotCont>), dim3(grid), dim3(256), 0, as_stream(stream), a);
   });
   DL_RETURN_LAUNCH("dl_embed_cont_bwd");
+}
+
+extern "C" int dl_embed_cont_bwd(const dl_emb_layout* L, const float* table, const float* cont,
+                                 const float* dz, const float* w_head, const float* fm_sum, float* cont_slab,
+                                 int32_t cont_slab_blocks, void* stream) {
+  return embed_cont_bwd_impl(L, table, cont, dz, w_head, fm_sum, cont_slab, cont_slab_blocks, nullptr, stream);
+}
+
+extern "C" int dl_embed_cont_bwd_fmdrop(const dl_emb_layout* L, const float* table, const float* cont,
+                                        const float* dz, const float* w_head, const float* fm_sum, float* cont_slab,
+                                        int32_t cont_slab_blocks, const dl_fm_drop* drop, void* stream) {
+  DL_CHECK_ARG(drop, "drop is NULL");
+  return embed_cont_bwd_impl(L, table, cont, dz, w_head, fm_sum, cont_slab, cont_slab_blocks, drop, stream);
 }

@@ -10,19 +10,37 @@
 // and the per-lane partial sums of dW = sum_b dz_b * feat_b.  Blocks leave
 // their partials in a slab that dl_adam_dense reduces (deterministic; no atomics).
 #include "common.h"
+#include "philox.h"
 
 namespace dl {
 
 constexpr int kHeadMaxFm = 128;   // FM columns (F + E)
 constexpr int kHeadMaxH4 = 4;     // hidden float4 chunks per lane: H <= 1024
 
+// FM-part dropout (include/dlamd.h "Dropout", layers DL_DROP_LAYER_FM1 / FM2): the lane that
+// loaded FM column c of a sample draws the column's keep bit and masks / scales the loaded value
+// before the reduction, so z, dz, dh and the slab's dz * feat sums all see the dropped features;
+// the wave's ballot of the keep bits goes to fm_keep[b][k] (bit c of word k = column 64 k + c)
+// for the FM backward kernels, which then need no RNG.  A threshold of 2^32 - 1 (keep = 1) keeps
+// every column without a compare.
+struct HeadDrop {
+  int F;                  // first-order columns [0, F), second-order [F, fm_cols)
+  uint32_t thr1, thr2;
+  float inv1, inv2;
+  uint2 key;
+  const float* opt;
+  unsigned long long* fm_keep;   // [B][2]
+};
+
+template <bool DROP>
 __global__ __launch_bounds__(256) void head_kernel(int B, int fm_cols, int H, const float* __restrict__ fm_out,
                                                    int fm_ld, const float* __restrict__ h, int ldh,
                                                    const float* __restrict__ w, const float* __restrict__ label,
                                                    float eps, float inv_batch, float* __restrict__ score,
                                                    float* __restrict__ z_out, float* __restrict__ dz,
-                                                   float* __restrict__ dh, float* __restrict__ slab) {
+                                                   float* __restrict__ dh, float* __restrict__ slab, HeadDrop dr) {
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const uint32_t step = DROP ? drop_step(dr.opt) : 0u;
   const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   const int nwaves = (gridDim.x * blockDim.x) >> 6;
   const int H4 = (H + 3) / 4;
@@ -64,6 +82,18 @@ __global__ __launch_bounds__(256) void head_kernel(int B, int fm_cols, int H, co
       for (int k = 0; k < kHeadMaxFm / 64; ++k) {
         const int c = lane + 64 * k;
         ff[i][k] = ok && c < fm_cols ? fm_out[(long long)b * fm_ld + c] : 0.f;
+        if (DROP) {
+          const bool first = c < dr.F;
+          const uint32_t thr = first ? dr.thr1 : dr.thr2;
+          bool kp = false;
+          if (ok && c < fm_cols)
+            kp = thr == 0xFFFFFFFFu ||
+                 drop_keep1((uint32_t)b, (uint32_t)(first ? c : c - dr.F),
+                            first ? (uint32_t)DL_DROP_LAYER_FM1 : (uint32_t)DL_DROP_LAYER_FM2, step, dr.key, thr);
+          ff[i][k] = kp ? ff[i][k] * (first ? dr.inv1 : dr.inv2) : 0.f;
+          const unsigned long long bits = __ballot(kp);
+          if (ok && lane == 0) dr.fm_keep[2 * (long long)b + k] = bits;
+        }
       }
       const float* hb = h + (long long)b * ldh;
 #pragma unroll
@@ -398,7 +428,31 @@ extern "C" int dl_head_fwd_bwd(int32_t B, int32_t fm_cols, int32_t H, const floa
   DL_CHECK_ARG(slab_blocks >= grid, "slab needs %d blocks", grid);
   if (B == 0) return 0;
   const size_t lds = 4 * (size_t)(fm_cols + H + 2) * sizeof(float);
-  hipLaunchKernelGGL(head_kernel, dim3(grid), dim3(256), lds, as_stream(stream), B, fm_cols, H,
-                     fm_out, fm_ld, h, ldh, w, label, eps, inv_batch, score, z_out, dz, dh, slab);
+  hipLaunchKernelGGL(head_kernel<false>, dim3(grid), dim3(256), lds, as_stream(stream), B, fm_cols, H,
+                     fm_out, fm_ld, h, ldh, w, label, eps, inv_batch, score, z_out, dz, dh, slab, HeadDrop{});
   DL_RETURN_LAUNCH("dl_head_fwd_bwd");
+}
+
+extern "C" int dl_head_fwd_bwd_fmdrop(int32_t B, int32_t fm_cols, int32_t H, const float* fm_out, int32_t fm_ld,
+                                      const float* h, int32_t ldh, const float* w, const float* label, float eps,
+                                      float inv_batch, float* score, float* z_out, float* dz, float* dh, float* slab,
+                                      int32_t slab_blocks, int32_t F, uint32_t keep_thr1, float inv1,
+                                      uint32_t keep_thr2, float inv2, uint64_t seed, const float* opt,
+                                      uint64_t* fm_keep, void* stream) {
+  DL_CHECK_ARG(fm_cols > 0 && fm_cols <= kHeadMaxFm, "fm_cols %d not in [1, %d]", fm_cols, kHeadMaxFm);
+  DL_CHECK_ARG(F >= 0 && F <= fm_cols, "F %d not in [0, fm_cols %d]", F, fm_cols);
+  DL_CHECK_ARG(H > 0 && H <= 4 * 64 * kHeadMaxH4, "H %d > %d", H, 4 * 64 * kHeadMaxH4);
+  DL_CHECK_ARG(ldh % 4 == 0 && ldh >= H && ((uintptr_t)h % 16) == 0, "h must be 16-B aligned, ldh %% 4 == 0");
+  DL_CHECK_ARG(fm_out && opt && fm_keep && ((uintptr_t)fm_keep % 16) == 0, "fm_out, opt and a 16-B aligned fm_keep required");
+  DL_CHECK_ARG(inv1 >= 1.f && inv1 < 3.4e38f && inv2 >= 1.f && inv2 < 3.4e38f, "bad dropout factors %g %g",
+               (double)inv1, (double)inv2);
+  const int grid = dl_head_grid(B);
+  DL_CHECK_ARG(slab_blocks >= grid, "slab needs %d blocks", grid);
+  if (B == 0) return 0;
+  const size_t lds = 4 * (size_t)(fm_cols + H + 2) * sizeof(float);
+  const HeadDrop dr{F, keep_thr1, keep_thr2, inv1, inv2, make_uint2((uint32_t)seed, (uint32_t)(seed >> 32)), opt,
+                    reinterpret_cast<unsigned long long*>(fm_keep)};
+  hipLaunchKernelGGL(head_kernel<true>, dim3(grid), dim3(256), lds, as_stream(stream), B, fm_cols, H,
+                     fm_out, fm_ld, h, ldh, w, label, eps, inv_batch, score, z_out, dz, dh, slab, dr);
+  DL_RETURN_LAUNCH("dl_head_fwd_bwd_fmdrop");
 }

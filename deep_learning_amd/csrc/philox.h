@@ -1,5 +1,5 @@
 // Philox-4x32-10 counter-based RNG (Salmon et al., SC'11), shared by the parameter init
-// (optim.hip) and the deep tower's dropout mask (gemm_s3.hip, dropout.hip).
+// (optim.hip), the deep tower's dropout mask (gemm_s3.hip, dropout.hip) and the FM part's (head.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -27,6 +27,13 @@ __device__ __forceinline__ uint32_t drop_keep4(uint32_t row, uint32_t cg, uint32
   const uint4 r = philox(make_uint4(row, cg, layer, step), key);
   return (uint32_t)(r.x < thr) | ((uint32_t)(r.y < thr) << 1) | ((uint32_t)(r.z < thr) << 2) |
          ((uint32_t)(r.w < thr) << 3);
+}
+
+// The keep bit of the single element (row, col): the FM part's dropout (head.hip), where a lane
+// owns one FM column of a sample.
+__device__ __forceinline__ bool drop_keep1(uint32_t row, uint32_t col, uint32_t layer, uint32_t step, uint2 key,
+                                           uint32_t thr) {
+  return (drop_keep4(row, col >> 2, layer, step, key, thr) >> (col & 3u)) & 1u;
 }
 
 // the step the mask is drawn for: opt[7], the global step as a float (exact below 2^24), read on

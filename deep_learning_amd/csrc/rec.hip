@@ -439,11 +439,11 @@ __device__ __forceinline__ void rec_update(float* __restrict__ r, int E, int d, 
 // Per (sample, pooled slot): the gradient every member row of the slot receives,
 // (dx0[pool m] + dsec*(fm_sum - pooled_m)) / cnt  (div_no_nan; deepfm_multi_cate.py:71-111),
 // and dz * w_head[fm_col + m] / cnt_first for the first-order weights.
-template <int E>
+template <int E, bool DROP = false>
 __global__ __launch_bounds__(256) void pool_grad_kernel(dl_emb_layout L, dl_pool_desc p, const float* __restrict__ dz,
                                                         const float* __restrict__ w_head,
                                                         const float* __restrict__ fm_sum,
-                                                        const float* __restrict__ dx0, bool g1) {
+                                                        const float* __restrict__ dx0, bool g1, FmDrop dr) {
   constexpr int LPR = E / 4;
   const int S = L.cate_fields;
   const int Cf = (L.use_fm && L.fm_cont) ? L.cont_fields : 0;
@@ -456,14 +456,22 @@ __global__ __launch_bounds__(256) void pool_grad_kernel(dl_emb_layout L, dl_pool
     const float c = p.cnt_emb[bm];
     float4 gv = make_float4(0.f, 0.f, 0.f, 0.f);
     const float dzb = L.use_fm ? dz[b] : 0.f;
+    ulonglong2 kw = make_ulonglong2(0ull, 0ull);
+    if constexpr (DROP) kw = fm_keep_words(dr, b);
     if (c > 0.f) {
       float4 dp = *reinterpret_cast<const float4*>(dx0 + (long long)b * L.dx0_ld + p.dx0_pool_col + m * E + 4 * q);
       if (L.use_fm) {
         const float* ws = w_head + F + 4 * q;
         const float4 fs = *reinterpret_cast<const float4*>(fm_sum + (long long)b * E + 4 * q);
         const float4 pv = *reinterpret_cast<const float4*>(p.x0 + (long long)b * L.x0_ld + L.x0_pool_col + m * E + 4 * q);
-        dp.x = fmaf(dzb * ws[0], fs.x - pv.x, dp.x); dp.y = fmaf(dzb * ws[1], fs.y - pv.y, dp.y);
-        dp.z = fmaf(dzb * ws[2], fs.z - pv.z, dp.z); dp.w = fmaf(dzb * ws[3], fs.w - pv.w, dp.w);
+        if constexpr (DROP) {
+          const float4 ds = fm_dfm4(fm_keep_bits4(kw, F + 4 * q), dzb, make_float4(ws[0], ws[1], ws[2], ws[3]), dr.inv2);
+          dp.x = fmaf(ds.x, fs.x - pv.x, dp.x); dp.y = fmaf(ds.y, fs.y - pv.y, dp.y);
+          dp.z = fmaf(ds.z, fs.z - pv.z, dp.z); dp.w = fmaf(ds.w, fs.w - pv.w, dp.w);
+        } else {
+          dp.x = fmaf(dzb * ws[0], fs.x - pv.x, dp.x); dp.y = fmaf(dzb * ws[1], fs.y - pv.y, dp.y);
+          dp.z = fmaf(dzb * ws[2], fs.z - pv.z, dp.z); dp.w = fmaf(dzb * ws[3], fs.w - pv.w, dp.w);
+        }
       }
       gv = make_float4(dp.x / c, dp.y / c, dp.z / c, dp.w / c);
     }
@@ -471,7 +479,10 @@ __global__ __launch_bounds__(256) void pool_grad_kernel(dl_emb_layout L, dl_pool
     *reinterpret_cast<float4*>(p.g_pool + bm * gp + 4 * q) = gv;
     if (g1 && q == 0) {
       const float c1 = p.cnt_first[bm];
-      p.g1_pool[bm * (p.g_pitch > 0 ? p.g_pitch : 1)] = c1 > 0.f ? dzb * w_head[p.fm_col + m] / c1 : 0.f;
+      p.g1_pool[bm * (p.g_pitch > 0 ? p.g_pitch : 1)] =
+          c1 <= 0.f ? 0.f
+          : DROP    ? fm_dfm(fm_keep_bit(kw, p.fm_col + m), dzb, w_head[p.fm_col + m], dr.inv1) / c1
+                    : dzb * w_head[p.fm_col + m] / c1;
     }
   }
 }
@@ -667,7 +678,7 @@ __device__ __forceinline__ void hot_scan_block(const SegGradIn& sg, const HotWs&
 // MULTI (multi-hot references present, C3): the pooled slot of a position from an LDS table,
 // and each row's references fetched four at a time (their loads in flight together: a
 // multi-hot row has ~2-3 references, each a dependent refs -> g_pool round trip); same sums.
-template <int E, bool STASH, bool MULTI = false>
+template <int E, bool STASH, bool MULTI = false, bool DROP = false>
 #ifndef DL_BWD_MIN_WAVES
 #define DL_BWD_MIN_WAVES 1
 #endif
@@ -732,15 +743,15 @@ __global__ __launch_bounds__(256, STASH ? DL_BWD_MIN_WAVES : 1) void rec_bwd_ada
     float w = 0.f, wm = 0.f, wv = 0.f;
     rec_bwd_state<E, STASH>(row, n_rep + u, q, first, row_ok, rec, rows_u, rows_u1, mv, c, t, ring, p, m, v, w, wm,
                             wv);
-    const SegGrad4 s = MULTI ? segment_grad4_range_pf<E>(sg, cr.e0, cr.e1, kc, q, nrefs, wsec)
-                             : segment_grad4_range<E>(sg, cr.e0, cr.e1, kc, q, nrefs, wsec);
+    const SegGrad4 s = MULTI ? segment_grad4_range_pf<E, DROP>(sg, cr.e0, cr.e1, kc, q, nrefs, wsec)
+                             : segment_grad4_range<E, DROP>(sg, cr.e0, cr.e1, kc, q, nrefs, wsec);
     if (!row_ok) continue;
     rec_bwd_apply<E>(s, row, q, first, p, m, v, w, wm, wv, rec, c, L, n_rep, g_rep, g1_rep, alpha, t);
   }
 }
 
 // Pass 2: the rows whose segments have more than kSegLong references, one whole block each.
-template <int E>
+template <int E, bool DROP = false>
 __global__ __launch_bounds__(256) void rec_bwd_long_kernel(DL_REC_BWD_PARAMS) {
   if (step_poisoned(opt)) return;
   rec_load_hyper(c, opt);
@@ -761,7 +772,7 @@ __global__ __launch_bounds__(256) void rec_bwd_long_kernel(DL_REC_BWD_PARAMS) {
   const int t = (int)opt[7];
   const float alpha = opt[3];
   const bool first = c.has_first && q == 0;
-  for_long_segments<E>(sg, nu, nrefs, wsec, sh, [&](long long u, const SegGrad4& s) {
+  for_long_segments<E, DROP>(sg, nu, nrefs, wsec, sh, [&](long long u, const SegGrad4& s) {
     const int64_t row = decode_key(uniq[u], world);
     const bool row_ok = row >= 0 && row < L.n_rows;
     float4 p = make_float4(0.f, 0.f, 0.f, 0.f), m = p, v = p;
@@ -786,7 +797,7 @@ __global__ __launch_bounds__(1024) void rec_hot_scan_kernel(SegGradIn sg, HotWs 
   hot_scan_block(sg, h, clamp_uniq(n_uniq, nrefs, sg.status), nrefs);
 }
 
-template <int E>
+template <int E, bool DROP = false>
 __global__ __launch_bounds__(256) void rec_hot_chunk_kernel(SegGradIn sg, HotWs h, const int32_t* __restrict__ n_uniq,
                                                             const float* __restrict__ opt) {
   if (step_poisoned(opt)) return;
@@ -809,7 +820,7 @@ __global__ __launch_bounds__(256) void rec_hot_chunk_kernel(SegGradIn sg, HotWs 
     const int c = t - h.off[i];
     const SegRange r = seg_range(sg, h.list[i], nu, nrefs);
     const int c0 = r.e0 + c * kSegChunk;
-    const SegGrad4 p = segment_grad4_block<E>(sg, c0, min(r.e1, c0 + kSegChunk), nrefs, wsec, sh);
+    const SegGrad4 p = segment_grad4_block<E, DROP>(sg, c0, min(r.e1, c0 + kSegChunk), nrefs, wsec, sh);
     if (threadIdx.x < E / 4) {
       float4* o = reinterpret_cast<float4*>(h.part + (long long)t * PF) + 3 * q;
       o[0] = p.s; o[1] = p.x; o[2] = p.dsum;
@@ -1222,16 +1233,22 @@ extern "C" int64_t dl_rec_bwd_workspace_bytes(int64_t nrefs, int32_t emb_dim) {
   return nrefs > 0 && emb_dim > 0 ? hot_ws_bytes(nrefs, emb_dim) : 0;
 }
 
-extern "C" int dl_rec_bwd_adam(const dl_emb_layout* L, float* rec, int32_t rec_ld, int32_t rec_flags, int32_t n_rep,
-                               const float* rows_u, const float* rows_u1, const float* mv_u,
-                               const uint32_t* uniq_keys, const int32_t* seg_off, const int32_t* n_uniq,
-                               const int32_t* sorted_refs, int32_t world, int64_t max_uniq, const float* dz,
-                               const float* w_head, const float* fm_sum, const float* dx0, float* g_rep,
-                               float* g1_rep, const float* hist, int32_t hist_len, const float* opt,
-                               const dl_pool_desc* pool, void* hot_ws_ptr, int64_t hot_ws_size, void* stream) {
+// DROP: the FM-part dropout twins (dl_rec_bwd_adam_fmdrop; segment.h "FM-part dropout") — the
+// plain instantiations are the kernels they were.
+template <bool DROP>
+static int rec_bwd_adam_impl(const dl_emb_layout* L, float* rec, int32_t rec_ld, int32_t rec_flags, int32_t n_rep,
+                             const float* rows_u, const float* rows_u1, const float* mv_u,
+                             const uint32_t* uniq_keys, const int32_t* seg_off, const int32_t* n_uniq,
+                             const int32_t* sorted_refs, int32_t world, int64_t max_uniq, const float* dz,
+                             const float* w_head, const float* fm_sum, const float* dx0, float* g_rep,
+                             float* g1_rep, const float* hist, int32_t hist_len, const float* opt,
+                             const dl_pool_desc* pool, void* hot_ws_ptr, int64_t hot_ws_size, const dl_fm_drop* drop,
+                             void* stream) {
   const int32_t has_first = rec_flags & DL_REC_FIRST;
   DL_CHECK_ARG(L && rec && rows_u && uniq_keys && seg_off && n_uniq && sorted_refs && dx0 && opt,
                "NULL argument");
+  DL_CHECK_ARG(!DROP || drop, "drop is NULL");
+  if (int rc = fm_drop_check(L, DROP ? drop : nullptr)) return rc;
   const long long nrefs_all = (long long)L->batch * index_slots(*L);
   DL_CHECK_ARG(!hot_ws_ptr || (hot_ws_size >= hot_ws_bytes(nrefs_all, L->emb_dim) && (uintptr_t)hot_ws_ptr % 16 == 0),
                "hot-row workspace: %lld bytes needed (dl_rec_bwd_workspace_bytes), 16-B aligned",
@@ -1256,6 +1273,7 @@ extern "C" int dl_rec_bwd_adam(const dl_emb_layout* L, float* rec, int32_t rec_l
                "g_pitch %d: 0 or >= E + 1 and a multiple of 4", multi ? pool->g_pitch : 0);
   SegGradIn sg{*L, seg_off, sorted_refs, dz, w_head, fm_sum, dx0};
   sg.status = reinterpret_cast<int*>(const_cast<float*>(opt) + DL_OPT_STATUS);   // opt_status(opt), host side
+  if (DROP) sg.drop = fm_drop_of(drop);
   const bool g1p = multi && L->use_fm && has_first;
   if (multi) {
     sg.slot_start = pool->slot_start; sg.slot_end = pool->slot_end; sg.n_slots = pool->n_slots;
@@ -1264,8 +1282,8 @@ extern "C" int dl_rec_bwd_adam(const dl_emb_layout* L, float* rec, int32_t rec_l
     sg.g1_stride = pool->g_pitch > 0 ? pool->g_pitch : 1;
     if (L->batch > 0)
       DL_DISPATCH_E(L->emb_dim, {
-        hipLaunchKernelGGL(pool_grad_kernel<kE>, dim3(grid_cap((long long)L->batch * pool->n_slots * (kE / 4))),
-                           dim3(256), 0, as_stream(stream), *L, *pool, dz, w_head, fm_sum, dx0, g1p);
+        hipLaunchKernelGGL((pool_grad_kernel<kE, DROP>), dim3(grid_cap((long long)L->batch * pool->n_slots * (kE / 4))),
+                           dim3(256), 0, as_stream(stream), *L, *pool, dz, w_head, fm_sum, dx0, g1p, sg.drop);
       });
   }
   DL_DISPATCH_E(L->emb_dim, {
@@ -1273,8 +1291,9 @@ extern "C" int dl_rec_bwd_adam(const dl_emb_layout* L, float* rec, int32_t rec_l
 #ifdef DL_BWD_GRID_CAP
     if (grid > DL_BWD_GRID_CAP) grid = DL_BWD_GRID_CAP;
 #endif
-    auto bwd = (DL_BWD_STASH_SPECIAL && mv_u) ? (multi ? rec_bwd_adam_kernel<kE, true, true> : rec_bwd_adam_kernel<kE, true>)
-                                              : rec_bwd_adam_kernel<kE, false>;
+    auto bwd = (DL_BWD_STASH_SPECIAL && mv_u)
+                   ? (multi ? rec_bwd_adam_kernel<kE, true, true, DROP> : rec_bwd_adam_kernel<kE, true, false, DROP>)
+                   : rec_bwd_adam_kernel<kE, false, false, DROP>;
     hipStream_t st = as_stream(stream);
     const RecCfg rc = make_rec_cfg(kE, rec_ld, rec_flags, (mv_u ? 2 : hist_len));
     if (hot_ws_ptr) {
@@ -1284,7 +1303,7 @@ extern "C" int dl_rec_bwd_adam(const dl_emb_layout* L, float* rec, int32_t rec_l
                          mv_u, uniq_keys, n_uniq, world, g_rep, has_first ? g1_rep : nullptr, hist, opt, h.hdr);
       // the hot rows (none at uniform ids): chunks over the whole grid, then their updates
       hipLaunchKernelGGL(rec_hot_scan_kernel, dim3(1), dim3(1024), 0, st, sg, h, n_uniq, opt);
-      hipLaunchKernelGGL(rec_hot_chunk_kernel<kE>, dim3(1024), dim3(256), 0, st, sg, h, n_uniq, opt);
+      hipLaunchKernelGGL((rec_hot_chunk_kernel<kE, DROP>), dim3(1024), dim3(256), 0, st, sg, h, n_uniq, opt);
       hipLaunchKernelGGL(rec_hot_apply_kernel<kE>, dim3(64), dim3(256), 0, st, sg, rec, rc, n_rep, rows_u,
                          has_first ? rows_u1 : nullptr, mv_u, uniq_keys, world, g_rep, has_first ? g1_rep : nullptr,
                          hist, opt, h);
@@ -1292,12 +1311,37 @@ extern "C" int dl_rec_bwd_adam(const dl_emb_layout* L, float* rec, int32_t rec_l
       hipLaunchKernelGGL(bwd, dim3(grid), dim3(256), 0, st, sg, rec, rc, n_rep, rows_u, has_first ? rows_u1 : nullptr,
                          mv_u, uniq_keys, n_uniq, world, g_rep, has_first ? g1_rep : nullptr, hist, opt, nullptr);
       // the hot rows' long segments (none at uniform ids: one scan of the segment offsets)
-      hipLaunchKernelGGL(rec_bwd_long_kernel<kE>, dim3(1024), dim3(256), 0, st, sg, rec, rc, n_rep, rows_u,
+      hipLaunchKernelGGL((rec_bwd_long_kernel<kE, DROP>), dim3(1024), dim3(256), 0, st, sg, rec, rc, n_rep, rows_u,
                          has_first ? rows_u1 : nullptr, mv_u, uniq_keys, n_uniq, world, g_rep,
                          has_first ? g1_rep : nullptr, hist, opt, nullptr);
     }
   });
-  DL_RETURN_LAUNCH("dl_rec_bwd_adam");
+  DL_RETURN_LAUNCH(DROP ? "dl_rec_bwd_adam_fmdrop" : "dl_rec_bwd_adam");
+}
+
+extern "C" int dl_rec_bwd_adam(const dl_emb_layout* L, float* rec, int32_t rec_ld, int32_t rec_flags, int32_t n_rep,
+                               const float* rows_u, const float* rows_u1, const float* mv_u,
+                               const uint32_t* uniq_keys, const int32_t* seg_off, const int32_t* n_uniq,
+                               const int32_t* sorted_refs, int32_t world, int64_t max_uniq, const float* dz,
+                               const float* w_head, const float* fm_sum, const float* dx0, float* g_rep,
+                               float* g1_rep, const float* hist, int32_t hist_len, const float* opt,
+                               const dl_pool_desc* pool, void* hot_ws_ptr, int64_t hot_ws_size, void* stream) {
+  return rec_bwd_adam_impl<false>(L, rec, rec_ld, rec_flags, n_rep, rows_u, rows_u1, mv_u, uniq_keys, seg_off, n_uniq,
+                                  sorted_refs, world, max_uniq, dz, w_head, fm_sum, dx0, g_rep, g1_rep, hist, hist_len,
+                                  opt, pool, hot_ws_ptr, hot_ws_size, nullptr, stream);
+}
+
+extern "C" int dl_rec_bwd_adam_fmdrop(const dl_emb_layout* L, float* rec, int32_t rec_ld, int32_t rec_flags,
+                                      int32_t n_rep, const float* rows_u, const float* rows_u1, const float* mv_u,
+                                      const uint32_t* uniq_keys, const int32_t* seg_off, const int32_t* n_uniq,
+                                      const int32_t* sorted_refs, int32_t world, int64_t max_uniq, const float* dz,
+                                      const float* w_head, const float* fm_sum, const float* dx0, float* g_rep,
+                                      float* g1_rep, const float* hist, int32_t hist_len, const float* opt,
+                                      const dl_pool_desc* pool, void* hot_ws_ptr, int64_t hot_ws_size,
+                                      const dl_fm_drop* drop, void* stream) {
+  return rec_bwd_adam_impl<true>(L, rec, rec_ld, rec_flags, n_rep, rows_u, rows_u1, mv_u, uniq_keys, seg_off, n_uniq,
+                                 sorted_refs, world, max_uniq, dz, w_head, fm_sum, dx0, g_rep, g1_rep, hist, hist_len,
+                                 opt, pool, hot_ws_ptr, hot_ws_size, drop, stream);
 }
 
 extern "C" int dl_rec_apply_rows(float* rec, int32_t rec_ld, int32_t emb_dim, int32_t rec_flags, int64_t row0,

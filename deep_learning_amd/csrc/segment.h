@@ -20,6 +20,54 @@
 
 namespace dl {
 
+// FM-part dropout on the backward (include/dlamd.h "Dropout", layers DL_DROP_LAYER_FM1 / FM2):
+// the head (dl_head_fwd_bwd_fmdrop) left every sample's keep bits in keep[b][2] (bit c of word k
+// = FM column 64 k + c), so wherever an FM backward forms dz[b] * w_head[col] it forms
+//   dfm = keep ? (dz[b] * w_head[col]) * inv : 0     (inv1: first order, inv2: second order)
+// instead — this order of multiplication in every kernel (explicit roundings, nothing left to
+// contraction), so the lazy, sorted and pooled forms stay bit-identical.  No RNG here.
+struct FmDrop {
+  const unsigned long long* keep;
+  float inv1, inv2;
+};
+
+// a sample's two keep words (16-B aligned)
+__device__ __forceinline__ ulonglong2 fm_keep_words(const FmDrop& d, long long b) {
+  return *reinterpret_cast<const ulonglong2*>(d.keep + 2 * b);
+}
+__device__ __forceinline__ bool fm_keep_bit(ulonglong2 w, int col) {
+  return ((col < 64 ? w.x : w.y) >> (col & 63)) & 1ull;
+}
+// the bits of columns col .. col + 3 (col + 3 < 128; they may straddle the two words)
+__device__ __forceinline__ uint32_t fm_keep_bits4(ulonglong2 w, int col) {
+  const int s = col & 63;
+  unsigned long long v = (col < 64 ? w.x : w.y) >> s;
+  if (col < 64 && s > 60) v |= w.y << (64 - s);
+  return (uint32_t)v & 15u;
+}
+__device__ __forceinline__ float fm_dfm(bool keep, float dzb, float w, float inv) {
+  return keep ? __fmul_rn(__fmul_rn(dzb, w), inv) : 0.f;
+}
+__device__ __forceinline__ float4 fm_dfm4(uint32_t kb, float dzb, float4 w, float inv) {
+  return make_float4(fm_dfm(kb & 1u, dzb, w.x, inv), fm_dfm(kb & 2u, dzb, w.y, inv), fm_dfm(kb & 4u, dzb, w.z, inv),
+                     fm_dfm(kb & 8u, dzb, w.w, inv));
+}
+
+// host side: the C ABI's descriptor (include/dlamd.h dl_fm_drop; NULL: no dropout) checked / converted
+inline int fm_drop_check(const dl_emb_layout* L, const dl_fm_drop* d) {
+  if (!d) return 0;
+  DL_CHECK_ARG(L->use_fm, "FM-part dropout needs an FM model");
+  DL_CHECK_ARG(d->fm_keep && ((uintptr_t)d->fm_keep % 16) == 0, "fm_keep must be non-NULL and 16-B aligned");
+  DL_CHECK_ARG(d->inv1 >= 1.f && d->inv1 < 3.4e38f && d->inv2 >= 1.f && d->inv2 < 3.4e38f,
+               "bad dropout factors %g %g", (double)d->inv1, (double)d->inv2);
+  DL_CHECK_ARG((L->fm_cont ? L->cont_fields : 0) + L->cate_fields + L->fm_extra + L->emb_dim <= 128,
+               "more than 128 FM columns");
+  return 0;
+}
+inline FmDrop fm_drop_of(const dl_fm_drop* d) {
+  return FmDrop{reinterpret_cast<const unsigned long long*>(d->fm_keep), d->inv1, d->inv2};
+}
+
 struct SegGradIn {
   dl_emb_layout L;
   const int32_t* seg_off;
@@ -44,6 +92,8 @@ struct SegGradIn {
   // optional: the pooled slot of every multi-hot position (slot_lut[l], n_slots = none), an LDS
   // table built by the kernel in place of the per-reference search over the slot ranges
   const unsigned char* slot_lut;
+  // FM-part dropout (the DROP instantiations only; last, so every other field keeps its place)
+  FmDrop drop;
 };
 
 // The pooled slot of multi-hot position l (n_slots when l lies in no slot).
@@ -135,7 +185,7 @@ __device__ __forceinline__ SegRange seg_range(const SegGradIn& a, long long u, l
 
 // Sums over the references e0..e1 of one row; k_first = refs[e0] when the caller has
 // already loaded it (software pipelining across rows), -2 to load it here.
-template <int E>
+template <int E, bool DROP = false>
 __device__ __forceinline__ SegGrad4 segment_grad4_range(const SegGradIn& a, int e0, int e1, int k_first, int q,
                                                         long long nrefs, float4 wsec, int stride = 1) {
   const dl_emb_layout& L = a.L;
@@ -164,11 +214,18 @@ __device__ __forceinline__ SegGrad4 segment_grad4_range(const SegGradIn& a, int 
     } else if (L.use_fm && sl < S) {
       const float dzb = a.dz[b];
       const float4 fs = *reinterpret_cast<const float4*>(a.fm_sum + (long long)((DL_BWD_DIAG & 2) ? 0 : b) * E + 4 * q);
-      const float4 ds = make_float4(dzb * wsec.x, dzb * wsec.y, dzb * wsec.z, dzb * wsec.w);
+      float4 ds;
+      if constexpr (DROP) {
+        const ulonglong2 kw = fm_keep_words(a.drop, b);
+        ds = fm_dfm4(fm_keep_bits4(kw, Cf + S + L.fm_extra + 4 * q), dzb, wsec, a.drop.inv2);
+        r.g1 = __fadd_rn(r.g1, fm_dfm(fm_keep_bit(kw, Cf + sl), dzb, a.w_head[Cf + sl], a.drop.inv1));
+      } else {
+        ds = make_float4(dzb * wsec.x, dzb * wsec.y, dzb * wsec.z, dzb * wsec.w);
+        r.g1 = fmaf(dzb, a.w_head[Cf + sl], r.g1);
+      }
       r.s.x = fmaf(ds.x, fs.x, r.s.x); r.s.y = fmaf(ds.y, fs.y, r.s.y);
       r.s.z = fmaf(ds.z, fs.z, r.s.z); r.s.w = fmaf(ds.w, fs.w, r.s.w);
       r.dsum.x += ds.x; r.dsum.y += ds.y; r.dsum.z += ds.z; r.dsum.w += ds.w;
-      r.g1 = fmaf(dzb, a.w_head[Cf + sl], r.g1);
     } else {
       const int f = L.use_fm ? sl - S : sl;
       const float4 gx = *reinterpret_cast<const float4*>(a.dx0 + (long long)((DL_BWD_DIAG & 1) ? 0 : b) * L.dx0_ld +
@@ -186,14 +243,15 @@ struct SegRef {
   int kind;     // 0 none, 1 pooled slot, 2 FM second order, 3 deep embedding
   float4 v;     // g_pool row / fm_sum row / dx0 row
   float dzb, w; // FM: dz[b], w_head[Cf + sl]; pooled: g1_pool (when present)
+  uint32_t kb;  // FM, DROP: keep bits of the second-order columns 4q .. 4q + 3 (bits 0-3), of the first-order one (4)
 };
 
-template <int E>
+template <int E, bool DROP = false>
 __device__ __forceinline__ SegRef seg_fetch(const SegGradIn& a, bool in, int k, int q, long long nrefs) {
   const dl_emb_layout& L = a.L;
   const int S = L.cate_fields, ns = index_slots(L), mb = index_multi_base(L);
   const int Cf = (L.use_fm && L.fm_cont) ? L.cont_fields : 0;
-  SegRef f{0, make_float4(0.f, 0.f, 0.f, 0.f), 0.f, 0.f};
+  SegRef f{0, make_float4(0.f, 0.f, 0.f, 0.f), 0.f, 0.f, 0u};
   if (!in) return f;
   if (k < 0 || k >= nrefs) {
     index_fault(a.status);
@@ -213,6 +271,10 @@ __device__ __forceinline__ SegRef seg_fetch(const SegGradIn& a, bool in, int k, 
     f.dzb = a.dz[b];
     f.v = *reinterpret_cast<const float4*>(a.fm_sum + (long long)((DL_BWD_DIAG & 2) ? 0 : b) * E + 4 * q);
     f.w = a.w_head[Cf + sl];
+    if constexpr (DROP) {
+      const ulonglong2 kw = fm_keep_words(a.drop, b);
+      f.kb = fm_keep_bits4(kw, Cf + S + L.fm_extra + 4 * q) | ((uint32_t)fm_keep_bit(kw, Cf + sl) << 4);
+    }
   } else {
     const int fi = L.use_fm ? sl - S : sl;
     f.kind = 3;
@@ -222,22 +284,30 @@ __device__ __forceinline__ SegRef seg_fetch(const SegGradIn& a, bool in, int k, 
   return f;
 }
 
-__device__ __forceinline__ void seg_acc(SegGrad4& r, const SegRef& f, float4 wsec, bool g1pool) {
+template <bool DROP = false>
+__device__ __forceinline__ void seg_acc(SegGrad4& r, const SegRef& f, float4 wsec, bool g1pool,
+                                        const FmDrop& dr = FmDrop{}) {
   if (f.kind == 1 || f.kind == 3) {
     r.x.x += f.v.x; r.x.y += f.v.y; r.x.z += f.v.z; r.x.w += f.v.w;
     if (f.kind == 1 && g1pool) r.g1 += f.w;
   } else if (f.kind == 2) {
-    const float4 ds = make_float4(f.dzb * wsec.x, f.dzb * wsec.y, f.dzb * wsec.z, f.dzb * wsec.w);
+    float4 ds;
+    if constexpr (DROP) {
+      ds = fm_dfm4(f.kb, f.dzb, wsec, dr.inv2);
+      r.g1 = __fadd_rn(r.g1, fm_dfm(f.kb & 16u, f.dzb, f.w, dr.inv1));
+    } else {
+      ds = make_float4(f.dzb * wsec.x, f.dzb * wsec.y, f.dzb * wsec.z, f.dzb * wsec.w);
+      r.g1 = fmaf(f.dzb, f.w, r.g1);
+    }
     r.s.x = fmaf(ds.x, f.v.x, r.s.x); r.s.y = fmaf(ds.y, f.v.y, r.s.y);
     r.s.z = fmaf(ds.z, f.v.z, r.s.z); r.s.w = fmaf(ds.w, f.v.w, r.s.w);
     r.dsum.x += ds.x; r.dsum.y += ds.y; r.dsum.z += ds.z; r.dsum.w += ds.w;
-    r.g1 = fmaf(f.dzb, f.w, r.g1);
   }
 }
 
 // segment_grad4_range with four references' loads in flight at a time (same sums, same
 // order): k_first = refs[e0] already loaded by the caller, or -2
-template <int E>
+template <int E, bool DROP = false>
 __device__ __forceinline__ SegGrad4 segment_grad4_range_pf(const SegGradIn& a, int e0, int e1, int k_first, int q,
                                                            long long nrefs, float4 wsec) {
   const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -253,9 +323,9 @@ __device__ __forceinline__ SegGrad4 segment_grad4_range_pf(const SegGradIn& a, i
     }
     SegRef f[4];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) f[i] = seg_fetch<E>(a, in[i], k[i], q, nrefs);
+    for (int i = 0; i < 4; ++i) f[i] = seg_fetch<E, DROP>(a, in[i], k[i], q, nrefs);
 #pragma unroll
-    for (int i = 0; i < 4; ++i) seg_acc(r, f[i], wsec, g1pool);
+    for (int i = 0; i < 4; ++i) seg_acc<DROP>(r, f[i], wsec, g1pool, a.drop);
   }
   return r;
 }
@@ -271,7 +341,7 @@ __device__ __forceinline__ SegGrad4 segment_grad4_range_pf(const SegGradIn& a, i
 #endif
 constexpr int kSegUnroll = DL_SEG_UNROLL;
 
-template <int E>
+template <int E, bool DROP = false>
 __device__ __forceinline__ SegGrad4 segment_grad4_strided(const SegGradIn& a, int e0, int e1, int stride, int q,
                                                           long long nrefs, float4 wsec) {
   constexpr int U = kSegUnroll;
@@ -291,12 +361,12 @@ __device__ __forceinline__ SegGrad4 segment_grad4_strided(const SegGradIn& a, in
     }
     SegRef f[U];
 #pragma unroll
-    for (int i = 0; i < U; ++i) f[i] = seg_fetch<E>(a, in[i], k[i], q, nrefs);
+    for (int i = 0; i < U; ++i) f[i] = seg_fetch<E, DROP>(a, in[i], k[i], q, nrefs);
     const int en = e + U * stride;
 #pragma unroll
     for (int i = 0; i < U; ++i) kn[i] = en + i * stride < e1 ? a.refs[en + i * stride] : -1;
 #pragma unroll
-    for (int i = 0; i < U; ++i) seg_acc(r, f[i], wsec, g1pool);
+    for (int i = 0; i < U; ++i) seg_acc<DROP>(r, f[i], wsec, g1pool, a.drop);
   }
   return r;
 }
@@ -337,12 +407,12 @@ struct SegLongLds {   // per block
 
 // One long segment summed by the whole block (every thread calls it); the total lands in
 // threads 0 .. E/4 - 1 (lane q = thread).
-template <int E>
+template <int E, bool DROP = false>
 __device__ __forceinline__ SegGrad4 segment_grad4_block(const SegGradIn& a, int e0, int e1, long long nrefs,
                                                         float4 wsec, SegLongLds& sh) {
   constexpr int LPR = E / 4, NS = 256 / LPR;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, q = tid % LPR;
-  SegGrad4 r = segment_grad4_strided<E>(a, e0 + tid / LPR, e1, NS, q, nrefs, wsec);
+  SegGrad4 r = segment_grad4_strided<E, DROP>(a, e0 + tid / LPR, e1, NS, q, nrefs, wsec);
   seg_wave_butterfly<LPR>(r);
   if (lane < LPR) {
     sh.s[wv][lane] = r.s; sh.x[wv][lane] = r.x; sh.d[wv][lane] = r.dsum;
@@ -371,19 +441,19 @@ __device__ __forceinline__ void seg_add(SegGrad4& t, const SegGrad4& c) {
   t.g1 += c.g1;
 }
 
-template <int E>
+template <int E, bool DROP = false>
 __device__ __forceinline__ SegGrad4 segment_grad4_chunked(const SegGradIn& a, int e0, int e1, long long nrefs,
                                                           float4 wsec, SegLongLds& sh) {
-  SegGrad4 t = segment_grad4_block<E>(a, e0, min(e1, e0 + kSegChunk), nrefs, wsec, sh);
+  SegGrad4 t = segment_grad4_block<E, DROP>(a, e0, min(e1, e0 + kSegChunk), nrefs, wsec, sh);
   for (int c0 = e0 + kSegChunk; c0 < e1; c0 += kSegChunk)
-    seg_add(t, segment_grad4_block<E>(a, c0, min(e1, c0 + kSegChunk), nrefs, wsec, sh));
+    seg_add(t, segment_grad4_block<E, DROP>(a, c0, min(e1, c0 + kSegChunk), nrefs, wsec, sh));
   return t;
 }
 
 // Second pass over the long segments: block b scans its share of the unique rows for
 // segments of more than kSegLong references and calls fn(u, sums) for each, in threads
 // 0 .. E/4 - 1, after the whole block summed it.  Block-uniform; one barrier per 256 rows.
-template <int E, class Fn>
+template <int E, bool DROP = false, class Fn>
 __device__ __forceinline__ void for_long_segments(const SegGradIn& a, long long nu, long long nrefs, float4 wsec,
                                                   SegLongLds& sh, Fn&& fn) {
   const int tid = threadIdx.x;
@@ -401,7 +471,7 @@ __device__ __forceinline__ void for_long_segments(const SegGradIn& a, long long 
     for (int k = 0; k < n; ++k) {
       const long long uu = base + sh.u[k];
       const SegRange r = seg_range(a, uu, nu, nrefs);
-      const SegGrad4 t = segment_grad4_chunked<E>(a, r.e0, r.e1, nrefs, wsec, sh);
+      const SegGrad4 t = segment_grad4_chunked<E, DROP>(a, r.e0, r.e1, nrefs, wsec, sh);
       if (tid < E / 4) fn(uu, t);
     }
     __syncthreads();   // sh.n / sh.u before the next chunk

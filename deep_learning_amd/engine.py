@@ -74,11 +74,16 @@ class ModelSpec:
     the tower input and after every ReLU layer, deepfm_pipeline.py:148-153): len(hidden) + 1
     values in (0, 1], a longer list truncated (the reference's default holds 5 entries for 3
     layers); None or all ones: no dropout.
+    dropout_keep_fm: the reference's keep probabilities of the FM part (tf.nn.dropout on the
+    first-order products and on the second-order vector, deepfm_pipeline.py:98,110): two values in
+    (0, 1], a longer list truncated; None, with no effect, for all ones and for the models without
+    an FM part (dnn*, wdl), whose reference classes never read it.
     """
 
     def __init__(self, model, C=13, V=0, S=26, E=16, cate_index_size=1000, hidden=(400, 400, 400),
                  multi_ranges=(), Fw=0, lr=0.001, l2=1e-5, decay_steps=10000000, decay_rate=0.9,
-                 beta1=0.9, beta2=0.999, eps=1e-8, logloss_eps=1e-7, tower="f32", dropout_keep_deep=None):
+                 beta1=0.9, beta2=0.999, eps=1e-8, logloss_eps=1e-7, tower="f32", dropout_keep_deep=None,
+                 dropout_keep_fm=None):
         if model not in FAMILIES:
             raise ValueError("unsupported model %r" % model)
         fam = FAMILIES[model]
@@ -108,6 +113,15 @@ class ModelSpec:
                 raise ValueError("dropout_keep_deep values must lie in (0, 1], got %r" % (keep,))
             dropout_keep_deep = keep
         self.dropout_keep_deep = dropout_keep_deep
+        if dropout_keep_fm is not None:
+            keep = [float(k) for k in dropout_keep_fm]
+            if len(keep) < 2:
+                raise ValueError("dropout_keep_fm needs 2 values (first order, second order), got %d" % len(keep))
+            keep = keep[:2]
+            if not all(0.0 < k <= 1.0 for k in keep):
+                raise ValueError("dropout_keep_fm values must lie in (0, 1], got %r" % (keep,))
+            dropout_keep_fm = keep if fam["fm"] and any(k < 1.0 for k in keep) else None
+        self.dropout_keep_fm = dropout_keep_fm
 
     @property
     def dropout(self):
@@ -269,6 +283,12 @@ class CTREngine:
                 raise ValueError("dropout_keep_deep: input dropout (keep[0] < 1) is not supported for FM models "
                                  "with multi-hot slots (their FM backward reads the pooled vectors from x0, "
                                  "which the input dropout overwrites)")
+        # dropout of the FM part (ModelSpec.dropout_keep_fm): drawn by the head, which leaves the keep
+        # bits in fm_keep for the FM backward twins (include/dlamd.h "Dropout")
+        self.fmdrop = sp.dropout_keep_fm
+        if self.fmdrop and type(self) is not CTREngine:
+            raise ValueError("dropout_keep_fm: not supported by %s (the mask is indexed by the local "
+                             "row number; a sharded batch needs global rows)" % type(self).__name__)
         self.dev = torch.device(device)
         self.B = max_batch
         dev = self.dev
@@ -446,6 +466,11 @@ class CTREngine:
         self.dx0 = z(B, self.dx_ld)
         self.fm_out = z(B, self.fm_ld)
         self.fm_sum = z(B, E)
+        if self.fmdrop:
+            # the keep bits of a sample's FM columns, two words (bit c of word k: column 64 k + c)
+            self.fm_keep = torch.zeros(B, 2, dtype=torch.int64, device=dev)
+            self.fm_drop_desc = _lib.FmDrop(fm_keep=self.fm_keep.data_ptr(), inv1=self._keep_inv(self.fmdrop[0]),
+                                            inv2=self._keep_inv(self.fmdrop[1]))
         self.score, self.z, self.dz = z(B), z(B), z(B)
         self.head_grid = "dl_wdl_head_grid" if self.wdl else "dl_head_grid"   # slab rows per batch size
         self.head_blocks = call_int(self.head_grid, B)
@@ -988,6 +1013,21 @@ class CTREngine:
         e1.record()
         self.prof.append((label, e0, e1))
 
+    @staticmethod
+    def _keep_thr(keep):
+        return min(int(math.floor(keep * 4294967296.0)), 4294967295)
+
+    @staticmethod
+    def _keep_inv(keep):
+        return float(np.float32(1.0) / np.float32(keep))
+
+    def _fm_bwd(self, train_name):
+        """An FM backward entry point and its trailing arguments: the plain one, or its FM-part
+        dropout twin with the stored keep bits and the two factors."""
+        if self.fmdrop:
+            return train_name + "_fmdrop", (C_ref(self.fm_drop_desc),)
+        return train_name, ()
+
     def _drop_args(self, layer):
         """dl_gemm_s3_nt_drop / dl_dropout_apply's (keep_thr, inv, seed, layer, opt) of tensor
         `layer` (include/dlamd.h "Dropout": 0 = the tower input, l + 1 = hidden layer l's output)."""
@@ -1163,6 +1203,14 @@ class CTREngine:
                     sp.logloss_eps, 1.0 / B, ptr(self.score), ptr(self.z), ptr(self.dz), ptr(dh_last),
                     ptr(self.wg) if train else None, ptr(self.w_touched) if train else None,
                     ptr(self.head_slab), self.head_blocks, ptr(self.err), s)
+            return
+        if train and self.fmdrop:   # predict / evaluate never drop
+            k1, k2 = self.fmdrop
+            self._c("head", "dl_head_fwd_bwd_fmdrop", B, sp.fm_cols, H, ptr(self.fm_out), self.fm_ld, ptr(self.h[-1]),
+                    self.h_ld[-1], ptr(self.w_head), ptr(self.in_label), sp.logloss_eps, 1.0 / B,
+                    ptr(self.score), ptr(self.z), ptr(self.dz), ptr(self.dh[-1]), ptr(self.head_slab),
+                    self.head_blocks, sp.F, self._keep_thr(k1), self._keep_inv(k1), self._keep_thr(k2),
+                    self._keep_inv(k2), self.seed & 0xFFFFFFFFFFFFFFFF, ptr(self.opt), ptr(self.fm_keep), s)
             return
         self._c("head", "dl_head_fwd_bwd", B, sp.fm_cols, H, ptr(self.fm_out), self.fm_ld, ptr(self.h[-1]),
              self.h_ld[-1], ptr(self.w_head), ptr(self.in_label), sp.logloss_eps, 1.0 / B,
@@ -1366,24 +1414,28 @@ class CTREngine:
         if self.lazy:
             self._embed_bwd_lazy(B, L, s)
         elif self.bwd == "sorted":
-            self._c("embed_bwd", "dl_embed_bwd_sorted", C_ref(L), ptr(self.table), None, ptr(self.idx_uniq),
+            fn, fd = self._fm_bwd("dl_embed_bwd_sorted")
+            self._c("embed_bwd", fn, C_ref(L), ptr(self.table), None, ptr(self.idx_uniq),
                     ptr(self.idx_off), ptr(self.idx_n), ptr(self.idx_refs), 1, B * self.n_slot, ptr(self.dz),
                     ptr(self.w_head), ptr(self.fm_sum), ptr(self.dx0), ptr(self.tg), ptr(self.fmg),
-                    ptr(self.touched), 0, None, s)
-            self._c("cont_bwd", "dl_embed_cont_bwd", C_ref(L), ptr(self.table), ptr(self._cont()), ptr(self.dz),
-                    ptr(self.w_head), ptr(self.fm_sum), ptr(self.cont_slab), self.bwd_blocks, s)
+                    ptr(self.touched), 0, None, *fd, s)
+            fn, fd = self._fm_bwd("dl_embed_cont_bwd")
+            self._c("cont_bwd", fn, C_ref(L), ptr(self.table), ptr(self._cont()), ptr(self.dz),
+                    ptr(self.w_head), ptr(self.fm_sum), ptr(self.cont_slab), self.bwd_blocks, *fd, s)
         else:
-            self._c("embed_bwd", "dl_embed_bwd", C_ref(L), ptr(self.table), ptr(self.in_cate), ptr(self._cont()),
+            fn, fd = self._fm_bwd("dl_embed_bwd")
+            self._c("embed_bwd", fn, C_ref(L), ptr(self.table), ptr(self.in_cate), ptr(self._cont()),
                     ptr(self.dz), ptr(self.w_head), ptr(self.fm_sum), ptr(self.dx0), ptr(self.tg), ptr(self.fmg),
-                    ptr(self.touched), ptr(self.cont_slab), self.bwd_blocks, s)
+                    ptr(self.touched), ptr(self.cont_slab), self.bwd_blocks, *fd, s)
         if not self.lazy:
             self._c("cont_reduce", "dl_embed_cont_reduce", C_ref(L), ptr(self.cont_slab), bwd_blocks, ptr(self.tg),
                     ptr(self.fmg), ptr(self.touched), s)
         if sp.M and not self.lazy:
-            self._c("pool_bwd", "dl_pool_bwd", C_ref(L), ptr(self.in_cate), sp.S, ptr(self.slot_start), ptr(self.slot_end),
+            fn, fd = self._fm_bwd("dl_pool_bwd")
+            self._c("pool_bwd", fn, C_ref(L), ptr(self.in_cate), sp.S, ptr(self.slot_start), ptr(self.slot_end),
                  sp.M, self.fm_pool_col, ptr(self.x0), ptr(self.fm_sum), ptr(self.dz), ptr(self.w_head), ptr(self.dx0),
                  sp.S * sp.E, ptr(self.cnt_emb), ptr(self.cnt_first), ptr(self.tg), ptr(self.fmg),
-                 ptr(self.touched), s)
+                 ptr(self.touched), *fd, s)
         H = sp.hidden[-1]
         hb = call_int(self.head_grid, B)
         if self.wdl and self.wide_lazy:
@@ -1605,18 +1657,20 @@ class CTREngine:
         sp = self.spec
         bwd_blocks = call_int("dl_embed_bwd_grid", C_ref(L))
         E, R = sp.E, self.n_rep
-        self._c("embed_bwd", "dl_rec_bwd_adam", C_ref(L), ptr(self.rec), self.rec_ld, self.rec_flags, R,
+        fn, fd = self._fm_bwd("dl_rec_bwd_adam")
+        self._c("embed_bwd", fn, C_ref(L), ptr(self.rec), self.rec_ld, self.rec_flags, R,
                 ptr(self.rows_u), ptr(self.rows_u1), ptr(self.mv_u), ptr(self.idx_uniq), ptr(self.idx_off),
                 ptr(self.idx_n), ptr(self.idx_refs), 1, B * self.n_slot, ptr(self.dz), ptr(self.w_head),
                 ptr(self.fm_sum), ptr(self.dx0), ptr(self.g_rep), ptr(self.g1_rep), ptr(self.hist),
                 self.hist_len, ptr(self.opt), C_ref(self.pool_desc) if sp.M else None, ptr(self.hot_ws),
-                self.hot_ws.numel(), s)
+                self.hot_ws.numel(), *fd, s)
         if R:
             # FM cont-field rows: per-block register partials (on the blocks that hold samples),
             # folded into g_rep, then the rows updated
             cb = self._cont_blocks(B, bwd_blocks)
-            self._c("cont_bwd", "dl_embed_cont_bwd", C_ref(L), ptr(self.rows_u), ptr(self._cont()),
-                    ptr(self.dz), ptr(self.w_head), ptr(self.fm_sum), ptr(self.cont_slab), cb, s)
+            fn, fd = self._fm_bwd("dl_embed_cont_bwd")
+            self._c("cont_bwd", fn, C_ref(L), ptr(self.rows_u), ptr(self._cont()),
+                    ptr(self.dz), ptr(self.w_head), ptr(self.fm_sum), ptr(self.cont_slab), cb, *fd, s)
             self._c("cont_reduce", "dl_embed_cont_reduce", C_ref(L), ptr(self.cont_slab), cb,
                     ptr(self.g_rep), ptr(self.g1_rep), ptr(self.rep_touched), s)
             self._c("adam_rep", "dl_rec_apply_rows", ptr(self.rec), self.rec_ld, E, self.rec_flags, sp.fm_cont_offset, R,

@@ -6,7 +6,7 @@
 The 13 positional arguments mean what they mean in the reference.  Optional
 key=value overrides after them reach the hyper-parameters the reference
 hard-codes (batch_size, hidden_units=400,400,400, learning_rate, l2_reg,
-learning_rate_decay_steps/_rate, dropout_keep_deep=1,0.8,0.8,0.8, shuffle=0|1, shuffle_seed=N), so the
+learning_rate_decay_steps/_rate, dropout_keep_deep=1,0.8,0.8,0.8, dropout_keep_fm=0.9,0.8, shuffle=0|1, shuffle_seed=N), so the
 BASELINE configs (batch 65536, MLP [400]*3) are reachable from the same CLI.
 """
 import sys
@@ -38,6 +38,7 @@ class ModelParams:
         self.learning_rate = 0.001
         self.hidden_units = [512, 256, 128]
         self.dropout_keep_deep = [1, 1, 1, 1, 1]
+        self.dropout_keep_fm = [1, 1]
         self.learning_rate_decay_steps = 10000000
         self.learning_rate_decay_rate = 0.9
         self.l2_reg = 0.00001
@@ -48,8 +49,8 @@ class ModelParams:
             k, v = kv.split("=", 1)
             if k == "hidden_units":
                 self.hidden_units = [int(x) for x in v.split(",")]
-            elif k == "dropout_keep_deep":
-                self.dropout_keep_deep = [float(x) for x in v.split(",")]
+            elif k in ("dropout_keep_deep", "dropout_keep_fm"):
+                setattr(self, k, [float(x) for x in v.split(",")])
             elif k in ("batch_size", "learning_rate_decay_steps", "shuffle", "shuffle_seed"):
                 setattr(self, k, int(v))
             elif k in ("learning_rate", "l2_reg", "learning_rate_decay_rate"):

@@ -47,6 +47,9 @@ def _spec_from_args(model, args):
     keep = getattr(args, "dropout_keep_deep", None)
     if keep is not None:   # local_run.py:40; the engine drops only where a keep is below 1
         kw.update(dropout_keep_deep=[float(k) for k in keep])
+    keep_fm = getattr(args, "dropout_keep_fm", None)
+    if keep_fm is not None:   # the reference hard-codes [1, 1] in its model classes (deepfm_pipeline.py:31)
+        kw.update(dropout_keep_fm=[float(k) for k in keep_fm])
     return ModelSpec(model, **kw)
 
 

@@ -32,7 +32,8 @@ class DeepModel(LoadStyleModel):
                          E=self.embedding_size, cate_index_size=self.cate_feats_size, hidden=self.hidden_units,
                          lr=float(args.learning_rate), l2=float(args.l2_reg),
                          decay_steps=float(args.learning_rate_decay_steps),
-                         decay_rate=float(args.learning_rate_decay_rate))
+                         decay_rate=float(args.learning_rate_decay_rate),
+                         dropout_keep_fm=getattr(args, "dropout_keep_fm", None))
 
     def native_fields(self):
         f = [("labels", "label", 0, 1), ("cont_feats", "cont_feats", 0, self.cont_field_size),

@@ -408,6 +408,58 @@ int dl_gemm_s3_nt_drop(int32_t M, int32_t N, int32_t K, const float* A, int32_t 
 int dl_dropout_apply(float* x, int32_t M, int32_t N, int32_t ld, uint32_t keep_thr, float inv, uint64_t seed,
                      int32_t layer, const float* opt, uint8_t* mask_out, void* stream);
 
+/* Dropout of the FM part (the reference's dropout_keep_fm: tf.nn.dropout(first_order_mul, keep_fm[0])
+ * and tf.nn.dropout(second_order, keep_fm[1]), deepfm_pipeline.py:98,110).  The same function,
+ * key, threshold and inv; row is the sample's index in the batch, and two more layer ids, far
+ * from the tower's 0 .. len(hidden):
+ *   DL_DROP_LAYER_FM1: first order, col = the FM column j in [0, F), in fm_out's own column
+ *                      order (cont fields, cate fields, pooled slots);
+ *   DL_DROP_LAYER_FM2: second order, col = the embedding dim d in [0, E).
+ * A keep of exactly 1 (keep_thr = 2^32 - 1, inv = 1) keeps every element with factor 1 and no
+ * threshold compare is made, so keeps (1, k) leave the first-order part as without dropout.
+ *   forward:  fm_out'[b][j] = keep ? fm_out[b][j] * inv : 0 before the output layer (fm_out in
+ *             memory is not rewritten; fm_sum stays the undropped sum);
+ *   backward: dfm[b][j] = keep ? (dz[b] * w_head[j]) * inv : 0 replaces dz[b] * w_head[j]
+ *             wherever an FM backward forms that product — this order of multiplication in
+ *             every kernel; the second-order gradient is dfm[b][F + d] * (fm_sum[b][d] - v).
+ * dl_head_fwd_bwd_fmdrop: dl_head_fwd_bwd whose lanes draw the keep bit of the FM column they
+ *   loaded and mask / scale it before the reduction (z, score, dz, dh and the slab are those of
+ *   dl_head_fwd_bwd on the dropped features, bit for bit), and which writes the keep bits to
+ *   fm_keep [B][2] (16-B aligned): bit c of word k is column 64 k + c, columns >= fm_cols 0.
+ *   F: the first-order columns [0, F); the rest, [F, fm_cols), are the second order's.
+ * dl_fm_drop: what the FM backward twins read instead of drawing the mask again — the stored
+ *   bits and the two factors.  dl_embed_bwd_fmdrop, dl_embed_bwd_sorted_fmdrop,
+ *   dl_embed_cont_bwd_fmdrop, dl_pool_bwd_fmdrop and dl_rec_bwd_adam_fmdrop are their plain
+ *   namesakes with that descriptor before the stream; the plain entry points and their
+ *   kernels are unchanged. */
+#define DL_DROP_LAYER_FM1 (1 << 16)
+#define DL_DROP_LAYER_FM2 ((1 << 16) + 1)
+typedef struct dl_fm_drop {
+  const uint64_t* fm_keep; /* [B][2], written by dl_head_fwd_bwd_fmdrop */
+  float inv1;              /* first order: float32(1) / float32(keep_fm[0]) */
+  float inv2;              /* second order */
+} dl_fm_drop;
+int dl_embed_bwd_fmdrop(const dl_emb_layout* L, const float* table, const int64_t* cate,
+                        const float* cont, const float* dz, const float* w_head,
+                        const float* fm_sum, const float* dx0, float* g_table, float* g_first,
+                        uint8_t* touched, float* cont_slab, int32_t cont_slab_blocks, const dl_fm_drop* drop,
+                        void* stream);
+int dl_embed_cont_bwd_fmdrop(const dl_emb_layout* L, const float* table, const float* cont,
+                             const float* dz, const float* w_head, const float* fm_sum, float* cont_slab,
+                             int32_t cont_slab_blocks, const dl_fm_drop* drop, void* stream);
+int dl_embed_bwd_sorted_fmdrop(const dl_emb_layout* L, const float* table, const float* rows_u,
+                               const uint32_t* uniq_keys, const int32_t* seg_off, const int32_t* n_uniq,
+                               const int32_t* sorted_refs, int32_t world, int64_t max_uniq,
+                               const float* dz, const float* w_head, const float* fm_sum,
+                               const float* dx0, float* g_out, float* g1_out, uint8_t* touched,
+                               int32_t compact, const int32_t* upos, const dl_fm_drop* drop, void* stream);
+int dl_pool_bwd_fmdrop(const dl_emb_layout* L, const int64_t* ids, int32_t ids_col,
+                       const int32_t* slot_start, const int32_t* slot_end, int32_t n_slots,
+                       int32_t fm_col, const float* x0, const float* fm_sum, const float* dz,
+                       const float* w_head, const float* dx0, int32_t dx0_pool_col,
+                       const float* cnt_emb, const float* cnt_first, float* g_table,
+                       float* g_first, uint8_t* touched, const dl_fm_drop* drop, void* stream);
+
 /* ------------------------------------------------------------------------
  * Output layer + sigmoid + eps-log-loss, forward and backward fused
  * (deepfm_pipeline.py:157-183, dnn_pipeline.py:119-131):
@@ -420,6 +472,13 @@ int dl_head_fwd_bwd(int32_t B, int32_t fm_cols, int32_t H, const float* fm_out, 
                     const float* h, int32_t ldh, const float* w, const float* label,
                     float eps, float inv_batch, float* score, float* z_out, float* dz,
                     float* dh, float* slab, int32_t slab_blocks, void* stream);
+/* With FM-part dropout ("Dropout" above). */
+int dl_head_fwd_bwd_fmdrop(int32_t B, int32_t fm_cols, int32_t H, const float* fm_out, int32_t fm_ld,
+                           const float* h, int32_t ldh, const float* w, const float* label,
+                           float eps, float inv_batch, float* score, float* z_out, float* dz,
+                           float* dh, float* slab, int32_t slab_blocks, int32_t F, uint32_t keep_thr1, float inv1,
+                           uint32_t keep_thr2, float inv2, uint64_t seed, const float* opt, uint64_t* fm_keep,
+                           void* stream);
 int dl_head_grid(int32_t B);
 /* Blocks (= slab rows) of dl_wdl_head_fwd_bwd[_bf16] for batch B. */
 int dl_wdl_head_grid(int32_t B);
@@ -688,6 +747,15 @@ int dl_rec_bwd_adam(const dl_emb_layout* L, float* rec, int32_t rec_ld, int32_t 
                     const float* w_head, const float* fm_sum, const float* dx0, float* g_rep,
                     float* g1_rep, const float* hist, int32_t hist_len, const float* opt,
                     const dl_pool_desc* pool, void* hot_ws, int64_t hot_ws_bytes, void* stream);
+/* With FM-part dropout ("Dropout" above): the segment sums and the pooled-slot gradients take dfm. */
+int dl_rec_bwd_adam_fmdrop(const dl_emb_layout* L, float* rec, int32_t rec_ld, int32_t rec_flags, int32_t n_rep,
+                           const float* rows_u, const float* rows_u1, const float* mv_u,
+                           const uint32_t* uniq_keys, const int32_t* seg_off, const int32_t* n_uniq,
+                           const int32_t* sorted_refs, int32_t world, int64_t max_uniq, const float* dz,
+                           const float* w_head, const float* fm_sum, const float* dx0, float* g_rep,
+                           float* g1_rep, const float* hist, int32_t hist_len, const float* opt,
+                           const dl_pool_desc* pool, void* hot_ws, int64_t hot_ws_bytes, const dl_fm_drop* drop,
+                           void* stream);
 int64_t dl_rec_bwd_workspace_bytes(int64_t nrefs, int32_t emb_dim);
 /* Sharded owners without a sort: link every received position into its row's arrival
  * chain (head[local_rows] starts at -1; next[n]).  Then apply: one leader per row sums its

@@ -171,6 +171,10 @@ SIGNATURES = {
     "dl_rec_apply_chain": (I32, [P, I32, I32, I32, P, I64, P, P, P, P, P, I32, P, P]),
     "dl_auc_workspace_bytes": (I64, [I64]),
     "dl_auc": (I32, [P, I64, P, I64, I64, P, I64, P, P]),
+    "dl_gauc_workspace_bytes": (I64, [I64]),
+    "dl_gauc": (I32, [P, I64, P, I64, P, I64, I64, I32, P, I64, P, P]),
+    "dl_eval_stats_workspace_bytes": (I64, [I64]),
+    "dl_eval_stats": (I32, [P, I64, P, I64, I64, C.c_double, P, I64, P, P]),
     "dl_hbm_copy": (I32, [P, P, I64, P]),
     "dl_shard_gather_scalar": (I32, [P, P, I64, P, P]),
     "dl_shard_add_fixed": (I32, [P, P, I64, P, P, P]),

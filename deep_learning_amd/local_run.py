@@ -8,6 +8,10 @@ key=value overrides after them reach the hyper-parameters the reference
 hard-codes (batch_size, hidden_units=400,400,400, learning_rate, l2_reg,
 learning_rate_decay_steps/_rate, dropout_keep_deep=1,0.8,0.8,0.8, dropout_keep_fm=0.9,0.8, shuffle=0|1, shuffle_seed=N), so the
 BASELINE configs (batch 65536, MLP [400]*3) are reachable from the same CLI.
+
+Two more overrides choose what evaluation reports (deep_learning_amd/metrics.py); without them
+the output is the reference's: eval_metrics=auc,gauc,logloss,calibration (default auc) and
+gauc_slot=K, the cate_feats column whose id groups the samples for GAUC (the user-id slot).
 """
 import sys
 import time
@@ -55,10 +59,30 @@ class ModelParams:
                 setattr(self, k, int(v))
             elif k in ("learning_rate", "l2_reg", "learning_rate_decay_rate"):
                 setattr(self, k, float(v))
+            elif k == "gauc_slot":      # these two are stored only when given: the start-up dump stays as it is
+                self.gauc_slot = int(v)
+            elif k == "eval_metrics":
+                self.eval_metrics = [m for m in v.split(",") if m]
             else:
                 raise SystemExit("unknown override %s" % k)
         (self.cont_field_size, self.vector_feats_size, self.cate_field_size, self.multi_feats_size,
          self.multi_field_size, self.multi_feats_range) = my_utils.feat_size(self.feat_conf_path, self.alg_name)
+        check_eval_options(getattr(self, "eval_metrics", None), getattr(self, "gauc_slot", None), self.cate_field_size)
+
+
+EVAL_METRICS = ("auc", "gauc", "logloss", "calibration")
+
+
+def check_eval_options(eval_metrics, gauc_slot, cate_field_size):
+    """Refuses (SystemExit, the CLI's way) an unknown metric, gauc without gauc_slot and a slot
+    outside [0, cate_field_size)."""
+    for m in eval_metrics or ():
+        if m not in EVAL_METRICS:
+            raise SystemExit("eval_metrics: unknown metric %s (known: %s)" % (m, ",".join(EVAL_METRICS)))
+    if "gauc" in (eval_metrics or ()) and gauc_slot is None:
+        raise SystemExit("eval_metrics: gauc needs gauc_slot=K (the cate_feats column that holds the group id)")
+    if gauc_slot is not None and not 0 <= gauc_slot < int(cate_field_size):
+        raise SystemExit("gauc_slot=%d outside [0, cate_field_size=%d)" % (gauc_slot, int(cate_field_size)))
 
 
 def main(argv=None):
@@ -70,6 +94,7 @@ def main(argv=None):
         print("alg_name = %s is error" % mp.alg_name)
         sys.exit(-1)
     alg_model = __import__("deep_learning_amd.models." + mp.alg_name, fromlist=["DeepModel"])
+    eval_kw = {k: getattr(mp, k) for k in ("eval_metrics", "gauc_slot") if hasattr(mp, k)}
     if mp.action_type == "train":
         start_time = time.time()
         train_data = data_load.load_input_file(mp, mp.train_path, "train")
@@ -79,11 +104,11 @@ def main(argv=None):
         m.fit(mp.num_batch_size)
         end_time = time.time()
         print("model training time: %.2f s" % (end_time - start_time))
-        alg_model.predict(predict_data, mp.model_pb)
+        alg_model.predict(predict_data, mp.model_pb, **eval_kw)
     elif mp.action_type == "pred":
         print("--------------predict------------")
         predict_data = data_load.load_input_file(mp, mp.predict_path, "pred")
-        alg_model.predict(predict_data, mp.model_pb)
+        alg_model.predict(predict_data, mp.model_pb, **eval_kw)
     else:
         print("action_type = %s is error !!!" % mp.action_type)
 

@@ -5,6 +5,11 @@ sklearn.metrics.roc_auc_score, which the reference calls on the collected scores
 Scores stay on the device: the eval/predict loops hand their per-batch score tensors to
 an :class:`AucAccumulator` and one ``dl_auc`` call sorts and counts them.  Like sklearn,
 a label set with a single class raises ``ValueError``.
+
+Beside the pooled AUC: :func:`group_auc` (GAUC, ``dl_gauc`` — each group's own AUC, weighted by
+its impressions; the group id is any categorical slot, the user id for one), :func:`eval_stats`
+(log-loss and calibration, ``dl_eval_stats``) and :class:`EvalAccumulator`, which collects what
+all of them need batch by batch.
 """
 import numpy as np
 import torch
@@ -52,6 +57,109 @@ class AucAccumulator:
         if not self.scores:
             raise ValueError(_SINGLE_CLASS)
         return roc_auc(torch.cat(self.labels), torch.cat(self.scores))
+
+
+_NO_VALID_GROUP = "No group holds both classes. Group AUC is not defined in that case."
+_WEIGHTINGS = {"size": 0, "uniform": 1}
+
+
+def _dev_i64(x):
+    if isinstance(x, torch.Tensor):
+        return x.detach().to(device="cuda", dtype=torch.int64).reshape(-1)
+    return torch.from_numpy(np.ascontiguousarray(np.asarray(x, np.int64).reshape(-1))).cuda()
+
+
+def _strided_f32(x):
+    """A device f32 view and its element stride: a 1-D device f32 tensor is read where it lies."""
+    if isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 1 and x.stride(0) > 0:
+        return x.detach(), x.stride(0)
+    return _dev_f32(x), 1
+
+
+def group_auc(labels, scores, groups, weighting="size", details=False):
+    """GAUC: the mean over groups of each group's own AUC (``roc_auc`` on its samples alone),
+    weighted by the group's sample count (``"size"``) or equally (``"uniform"``), over the groups
+    that hold both classes.  ``groups`` are integer ids in [0, 2^31).  Host arrays or device
+    tensors.  ``details=True`` returns (gauc, {"covered_samples", "valid_groups", "groups"})."""
+    v, covered, valid, total = _gauc_call(labels, scores, groups, weighting)
+    if v != v:
+        raise ValueError(_NO_VALID_GROUP)
+    if details:
+        return v, {"covered_samples": covered, "valid_groups": valid, "groups": total}
+    return v
+
+
+def _gauc_call(labels, scores, groups, weighting):
+    """dl_gauc's four outputs (the GAUC NaN when no group is valid); raises on bad arguments."""
+    if weighting not in _WEIGHTINGS:
+        raise ValueError("weighting must be 'size' or 'uniform', got %r" % (weighting,))
+    (s, ss), (y, ys), g = _strided_f32(scores), _strided_f32(labels), _dev_i64(groups)
+    n = s.numel()
+    if y.numel() != n or g.numel() != n:
+        raise ValueError("labels, scores and groups differ in length")
+    if n == 0:
+        return float("nan"), 0, 0, 0
+    ws = torch.empty(int(_lib.lib().dl_gauc_workspace_bytes(n)), dtype=torch.uint8, device="cuda")
+    out = torch.empty(4, dtype=torch.float64, device="cuda")
+    call("dl_gauc", ptr(s), ss, ptr(y), ys, ptr(g), g.stride(0) if n > 1 else 1, n, _WEIGHTINGS[weighting], ptr(ws),
+         ws.numel(), ptr(out), _lib.stream_handle())
+    v, covered, valid, total = out.tolist()
+    if total != total:   # every output NaN: the error word (the workspace's first int32) says why
+        if int(ws[:4].view(torch.int32).item()) & _lib.STATUS_BAD_ID:
+            raise ValueError("group ids must lie in [0, 2**31)")
+        raise _lib.DLError("dl_gauc returned no result")
+    return v, int(covered), int(valid), int(total)
+
+
+def eval_stats(labels, scores, eps=1e-7):
+    """Log-loss (the reference's eps form, in double), calibration (sum of scores / positives),
+    mean score, positive rate and n of scores against 0/1 labels."""
+    (s, ss), (y, ys) = _strided_f32(scores), _strided_f32(labels)
+    n = s.numel()
+    if y.numel() != n:
+        raise ValueError("labels and scores differ in length")
+    if n == 0:
+        raise ValueError("no samples")
+    ws = torch.empty(int(_lib.lib().dl_eval_stats_workspace_bytes(n)) // 8, dtype=torch.float64, device="cuda")
+    out = torch.empty(4, dtype=torch.float64, device="cuda")
+    call("dl_eval_stats", ptr(s), ss, ptr(y), ys, n, float(eps), ptr(ws), ws.numel() * 8, ptr(out),
+         _lib.stream_handle())
+    loss, sp, sy, cnt = out.tolist()
+    cal = sp / sy if sy else (float("inf") if sp > 0 else float("nan"))
+    return {"logloss": loss / cnt, "calibration": cal, "mean_score": sp / cnt, "positive_rate": sy / cnt,
+            "n": int(cnt)}
+
+
+class EvalAccumulator(AucAccumulator):
+    """An AucAccumulator that also keeps the batches' group ids (when given): ``result()`` is
+    still the AUC; ``results()`` adds log-loss, calibration and — with groups — GAUC, each kernel
+    called once on the concatenation."""
+
+    def __init__(self, weighting="size"):
+        super().__init__()
+        self.groups = []
+        self.weighting = weighting
+
+    def add(self, labels, scores, groups=None):
+        super().add(labels, scores)
+        if (groups is None) != (not self.groups) and len(self.scores) > 1:
+            raise ValueError("groups must be given for every batch or for none")
+        if groups is not None:
+            g = _dev_i64(groups)
+            if g.numel() != self.scores[-1].numel():
+                raise ValueError("labels, scores and groups differ in length")
+            self.groups.append(g)
+
+    def results(self):
+        if not self.scores:
+            raise ValueError(_SINGLE_CLASS)
+        y, s = torch.cat(self.labels), torch.cat(self.scores)
+        st = eval_stats(y, s)
+        out = {"auc": roc_auc(y, s), "logloss": st["logloss"], "calibration": st["calibration"]}
+        if self.groups:
+            v, d = group_auc(y, s, torch.cat(self.groups), weighting=self.weighting, details=True)
+            out.update(gauc=v, gauc_covered=d["covered_samples"], gauc_groups=d["valid_groups"])
+        return out
 
 
 class ShardedAucAccumulator(AucAccumulator):

@@ -32,7 +32,7 @@ import torch
 import inspect
 
 from ..engine import FAMILIES, CTREngine, ModelSpec, default_adam
-from ..metrics import AucAccumulator
+from ..metrics import AucAccumulator, EvalAccumulator
 
 
 def _spec_from_args(model, args):
@@ -51,6 +51,29 @@ def _spec_from_args(model, args):
     if keep_fm is not None:   # the reference hard-codes [1, 1] in its model classes (deepfm_pipeline.py:31)
         kw.update(dropout_keep_fm=[float(k) for k in keep_fm])
     return ModelSpec(model, **kw)
+
+
+def _eval_options(eval_metrics, gauc_slot):
+    """The extra metrics asked for (eval_metrics without auc, in its order) and the group slot
+    (None unless gauc is among them)."""
+    extra = [m for m in (eval_metrics or ()) if m != "auc"]
+    for m in extra:
+        if m not in ("gauc", "logloss", "calibration"):
+            raise ValueError("eval_metrics: unknown metric %s" % m)
+    if "gauc" in extra and gauc_slot is None:
+        raise ValueError("eval_metrics: gauc needs gauc_slot (the cate_feats column that holds the group id)")
+    return extra, (int(gauc_slot) if "gauc" in extra else None)
+
+
+def _group_ids(cate, slot):
+    cate = cate if isinstance(cate, torch.Tensor) else np.asarray(cate)
+    if not 0 <= slot < cate.shape[1]:
+        raise ValueError("gauc_slot=%d outside [0, %d)" % (slot, cate.shape[1]))
+    return cate[:, slot]
+
+
+def _extra_fields(extra, res, fmt, prefix):
+    return [prefix + "%s:%s" % (m, fmt % res[m]) for m in extra]
 
 
 class CTRModel:
@@ -109,6 +132,9 @@ class CTRModel:
                 loss = loss_fn()
                 auc = self.eval(None, val_data)
                 print("[{}] val_auc:{}\t loss:{} time:{:.2f}s".format(i, auc, loss, batch_end_time - start_time))
+                extra = _eval_options(getattr(self.args, "eval_metrics", None), getattr(self.args, "gauc_slot", None))[0]
+                if extra:
+                    print("[{}] ".format(i) + " ".join(_extra_fields(extra, self.last_eval, "%s", "val_")))
                 sys.stdout.flush()
                 start_time = time.time()
                 batch_count = 0
@@ -139,15 +165,24 @@ class CTRModel:
     def eval(self, sess, val_data):
         if self.engine is None:
             self.model_optimizer()
-        acc = AucAccumulator()
+        extra, slot = _eval_options(getattr(self.args, "eval_metrics", None), getattr(self.args, "gauc_slot", None))
+        acc = EvalAccumulator() if extra else AucAccumulator()
         for i in range(len(val_data[0])):
             batch = {"label": val_data[0][i], "cate_feats": val_data[2][i]}
             if val_data[1][i] is not None:
                 batch["cont_feats"] = val_data[1][i]
             if val_data[3][i] is not None:
                 batch["vector_feats"] = val_data[3][i]
-            acc.add(val_data[0][i], _predict_batches(self.engine, batch))
-        return acc.result()
+            scores = _predict_batches(self.engine, batch)
+            if slot is not None:
+                acc.add(val_data[0][i], scores, _group_ids(val_data[2][i], slot))
+            else:
+                acc.add(val_data[0][i], scores)
+        if not extra:
+            return acc.result()
+        res = acc.results()
+        self.last_eval = {m: res[m] for m in ["auc"] + extra}
+        return res["auc"]
 
     # --------------------------------------------------------------- checkpoints
     def _save_checkpoint(self, directory):
@@ -266,17 +301,26 @@ def load_model(model_pb, max_batch=None):
     return eng
 
 
-def predict(predict_data, model_pb):
-    """Loads the exported model and scores predict_data (deepfm_pipeline.py:314-346)."""
+def predict(predict_data, model_pb, eval_metrics=None, gauc_slot=None):
+    """Loads the exported model and scores predict_data (deepfm_pipeline.py:314-346).
+    eval_metrics / gauc_slot (local_run's overrides of the same names): further metrics, each
+    printed on a line of its own after the AUC's."""
     eng = None
-    acc = AucAccumulator()
+    extra, slot = _eval_options(eval_metrics, gauc_slot)
+    acc = EvalAccumulator() if extra else AucAccumulator()
     for b in predict_data:
         if eng is None:
             eng = load_model(model_pb, max_batch=np.asarray(b["label"]).shape[0])
-        acc.add(b["label"], _predict_batches(eng, b))
+        if slot is not None:
+            acc.add(b["label"], _predict_batches(eng, b), _group_ids(b["cate_feats"], slot))
+        else:
+            acc.add(b["label"], _predict_batches(eng, b))
     print("-----------end of data_set-----------")
-    auc = acc.result()
+    res = acc.results() if extra else {"auc": acc.result()}
+    auc = res["auc"]
     print("val of auc:%.5f" % auc)
+    for line in _extra_fields(extra, res, "%.5f", "val of "):
+        print(line)
     sys.stdout.flush()
     print('---end---')
     return auc

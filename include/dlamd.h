@@ -934,6 +934,35 @@ int dl_init_random(float* p, int64_t n, int32_t dist, float mean, float scale, u
 int64_t dl_auc_workspace_bytes(int64_t n);
 int dl_auc(const float* scores, int64_t s_stride, const float* labels, int64_t l_stride, int64_t n,
            void* ws, int64_t ws_bytes, double* out, void* stream);
+/* Per-group AUC (GAUC, metrics.hip): the weighted mean over groups of each group's own tie-aware
+ * AUC (dl_auc's semantics on the group's samples alone: roc_auc_score per group).  A group is the
+ * set of samples with equal groups[i * g_stride] (int64, the dtype of cate_feats; ids in
+ * [0, 2^31)); it is valid iff it holds a positive and a negative (label > 0.5 = positive).  Ties
+ * are by the order-preserving float key (-0.0 ties with +0.0) and only within a group.
+ *   weighting 0: w_g = n_g, the group's sample count (impression-weighted GAUC);
+ *   weighting 1: w_g = 1 (mean of per-group AUC); anything else is refused on the host.
+ *   out[0] = sum_valid w_g AUC_g / sum_valid w_g (NaN when no group is valid)
+ *   out[1] = samples in valid groups, out[2] = valid groups, out[3] = all groups (exact integers).
+ * Every group's 2 x numerator = sum over its tie runs of pos (2 below + neg), below = the group's
+ * own negatives scored lower, and its counts are exact integers; floating point enters at
+ * w_g num2_g / (2 P_g N_g) per group, summed in double in a fixed order over the sorted group
+ * positions (per-tile partials, then one block): two calls on the same input give the same bits.
+ * An id outside [0, 2^31) is never read as another id: it raises the error word — the first
+ * int32 of ws, DL_STATUS_BAD_ID, rewritten by every call — and all of out[0..3] is NaN; the host
+ * turns the word into an exception (deep_learning_amd.metrics.group_auc: ValueError).
+ * Workspace: dl_gauc_workspace_bytes(n) (-1 for n <= 0 or n > 2^31-1), 256-B aligned. */
+int64_t dl_gauc_workspace_bytes(int64_t n);
+int dl_gauc(const float* scores, int64_t s_stride, const float* labels, int64_t l_stride, const int64_t* groups,
+            int64_t g_stride, int64_t n, int32_t weighting, void* ws, int64_t ws_bytes, double* out, void* stream);
+/* Log-loss and calibration sums of the same scores: p = the f32 score widened to double, y = the
+ * label bit (label > 0.5):
+ *   out[0] = sum -y log(p + eps) - (1 - y) log(1 - p + eps)   (the loss of dl_head_fwd_bwd, in double)
+ *   out[1] = sum p, out[2] = sum y, out[3] = n.
+ * Double sums in a fixed order, no atomics: per-block partials into ws, then one block sums them.
+ * Workspace: dl_eval_stats_workspace_bytes(n) (-1 for n <= 0 or n > 2^31-1), 8-B aligned. */
+int64_t dl_eval_stats_workspace_bytes(int64_t n);
+int dl_eval_stats(const float* scores, int64_t s_stride, const float* labels, int64_t l_stride, int64_t n, double eps,
+                  void* ws, int64_t ws_bytes, double* out, void* stream);
 /* Streaming copy of `bytes` (a multiple of 16, both pointers 16-B aligned) from src to dst: the
  * measured HBM yardstick bench.py reports beside the 8 TB/s specification (roofline.peak_measured). */
 int dl_hbm_copy(const void* src, void* dst, int64_t bytes, void* stream);

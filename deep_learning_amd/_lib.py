@@ -56,6 +56,7 @@ class FmDrop(C.Structure):
 DROP_LAYER_FM1, DROP_LAYER_FM2 = 1 << 16, (1 << 16) + 1
 OPT_LEN, OPT_STATUS, OPT_SKIP, OPT_BAD_STEP, OPT_BAD_COUNT, OPT_SEQ, OPT_BAD_RANKS = 32, 16, 17, 18, 19, 20, 21
 STATUS_BAD_ID, STATUS_LAG, STATUS_INDEX, STATUS_OVERFLOW, STATUS_DESYNC = 1, 2, 4, 8, 16
+STATUS_BAD_WEIGHT = 32
 REC_FIRST, REC_SPARSE_ADAM, REC_PLANE_SLOTS = 1, 2, 4
 ROWS_CLEAR_TOUCHED, ROWS_SPARSE_ADAM, ROWS_GRAD_FIXED = 1, 2, 4
 WIDE_GRAD_SCALE = 2.0 ** 48
@@ -136,6 +137,15 @@ SIGNATURES = {
     "dl_wdl_head_fwd_bwd": (I32, [I32, I32, I32, P, I32, P, I32, P, P, I64, P, F, F, P, P, P, P, P, P, P, I32, P, P]),
     "dl_wdl_head_fwd_bwd_bf16": (I32, [I32, I32, I32, P, I32, P, I32, P, P, I64, P, F, F, P, P, P, P, P, P, P, I32, P,
                                        P]),
+    "dl_weight_norm": (I32, [P, P, I32, F, P, P, P, P]),
+    "dl_head_fwd_bwd_weighted": (I32, [I32, I32, I32, P, I32, P, I32, P, P, F, P, P, P, P, P, P, P, I32, P]),
+    "dl_head_fwd_bwd_fmdrop_weighted": (I32, [I32, I32, I32, P, I32, P, I32, P, P, F, P, P, P, P, P, P, P, I32, I32,
+                                              U32, F, U32, F, U64, P, P, P]),
+    "dl_wdl_head_fwd_bwd_weighted": (I32, [I32, I32, I32, P, I32, P, I32, P, P, I64, P, F, P, P, P, P, P, P, P, P, P,
+                                           I32, P, P]),
+    "dl_wdl_head_fwd_bwd_bf16_weighted": (I32, [I32, I32, I32, P, I32, P, I32, P, P, I64, P, F, P, P, P, P, P, P, P,
+                                                P, P, I32, P, P]),
+    "dl_loss_accumulate_weighted": (I32, [P, I32, I32, I32, P, P, F, P, P, P]),
     "dl_slab_fold_rows": (I32, [P, I32, I32, I32, I32, P, I64, P, P]),
     "dl_adam_begin_step": (I32, [P, F, F, P]),
     "dl_step_guard": (I32, [P, P, P]),
@@ -175,6 +185,8 @@ SIGNATURES = {
     "dl_gauc": (I32, [P, I64, P, I64, P, I64, I64, I32, P, I64, P, P]),
     "dl_eval_stats_workspace_bytes": (I64, [I64]),
     "dl_eval_stats": (I32, [P, I64, P, I64, I64, C.c_double, P, I64, P, P]),
+    "dl_eval_stats_weighted_workspace_bytes": (I64, [I64]),
+    "dl_eval_stats_weighted": (I32, [P, I64, P, I64, P, I64, I64, C.c_double, P, I64, P, P]),
     "dl_hbm_copy": (I32, [P, P, I64, P]),
     "dl_shard_gather_scalar": (I32, [P, P, I64, P, P]),
     "dl_shard_add_fixed": (I32, [P, P, I64, P, P, P]),

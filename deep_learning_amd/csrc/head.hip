@@ -32,15 +32,27 @@ struct HeadDrop {
   unsigned long long* fm_keep;   // [B][2]
 };
 
-template <bool DROP>
+// Per-sample loss weights (include/dlamd.h "Sample weights"): the lane that loads label[b] loads the
+// sample's effective weight w_eff[b], and scale = w_eff[b] * inv_norm (one f32 multiply, inv_norm =
+// norm[0], dl_weight_norm's device normaliser) stands where the host constant inv_batch stands in
+// the unweighted form; the slab's loss column sums w_eff[b] * l_b.  All-ones weights give the
+// unweighted kernel's bits (1.0f * x is x, and inv_norm is the same f32 as the host's 1 / B).
+struct HeadWeight {
+  const float* w_eff;   // [B]
+  const float* norm;    // {inv_norm, N_nz}
+};
+
+template <bool DROP, bool WEIGHTED = false>
 __global__ __launch_bounds__(256) void head_kernel(int B, int fm_cols, int H, const float* __restrict__ fm_out,
                                                    int fm_ld, const float* __restrict__ h, int ldh,
                                                    const float* __restrict__ w, const float* __restrict__ label,
                                                    float eps, float inv_batch, float* __restrict__ score,
                                                    float* __restrict__ z_out, float* __restrict__ dz,
-                                                   float* __restrict__ dh, float* __restrict__ slab, HeadDrop dr) {
+                                                   float* __restrict__ dh, float* __restrict__ slab, HeadDrop dr,
+                                                   HeadWeight sw) {
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const uint32_t step = DROP ? drop_step(dr.opt) : 0u;
+  const float inv_norm = WEIGHTED ? sw.norm[0] : 0.f;
   const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   const int nwaves = (gridDim.x * blockDim.x) >> 6;
   const int H4 = (H + 3) / 4;
@@ -74,6 +86,7 @@ __global__ __launch_bounds__(256) void head_kernel(int B, int fm_cols, int H, co
     float ff[kAhead][kHeadMaxFm / 64];
     float4 hh[kAhead][kHeadMaxH4];
     float yy[kAhead];
+    float ww[WEIGHTED ? kAhead : 1];
 #pragma unroll
     for (int i = 0; i < kAhead; ++i) {
       const int b = b0 + i * nwaves;
@@ -102,6 +115,7 @@ __global__ __launch_bounds__(256) void head_kernel(int B, int fm_cols, int H, co
         hh[i][k] = ok && c4 < H4 ? *reinterpret_cast<const float4*>(hb + 4 * c4) : make_float4(0.f, 0.f, 0.f, 0.f);
       }
       yy[i] = ok ? label[b] : 0.f;
+      if (WEIGHTED) ww[i] = ok ? sw.w_eff[b] : 0.f;
     }
 #pragma unroll
     for (int i = 0; i < kAhead; ++i) {
@@ -116,14 +130,16 @@ __global__ __launch_bounds__(256) void head_kernel(int B, int fm_cols, int H, co
       const float z = wave_sum(part) + bias;
       const float p = 1.f / (1.f + expf(-z));
       const float y = yy[i];
-      const float dp = (-y / (p + eps) + (1.f - y) / (1.f - p + eps)) * inv_batch;
+      const float scale = WEIGHTED ? ww[WEIGHTED ? i : 0] * inv_norm : inv_batch;
+      const float dp = (-y / (p + eps) + (1.f - y) / (1.f - p + eps)) * scale;
       const float g = dp * p * (1.f - p);   // SigmoidGrad
       if (lane == 0) {
         score[b] = p;
         if (z_out) z_out[b] = z;
         dz[b] = g;
         gb += g;
-        lsum += -y * logf(p + eps) - (1.f - y) * logf(1.f - p + eps);
+        const float l = -y * logf(p + eps) - (1.f - y) * logf(1.f - p + eps);
+        lsum += WEIGHTED ? ww[WEIGHTED ? i : 0] * l : l;
       }
 #pragma unroll
       for (int k = 0; k < kHeadMaxFm / 64; ++k) gf[k] += g * ff[i][k];
@@ -199,7 +215,7 @@ __global__ __launch_bounds__(256) void head_kernel(int B, int fm_cols, int H, co
 #ifndef DL_WDL_HEAD_PF
 #define DL_WDL_HEAD_PF 0   // 1: prefetch the next sample's h row (measured neutral, C5 head 64 us both: profiles/r06f)
 #endif
-template <bool DHB, int H4M = kHeadMaxH4>
+template <bool DHB, int H4M = kHeadMaxH4, bool WEIGHTED = false>
 __global__ __launch_bounds__(256) void wdl_head_kernel(int B, int Fw, int H, const int64_t* __restrict__ wide,
                                                        int wide_ld, const float* __restrict__ h, int ldh,
                                                        const float* __restrict__ w, const float* __restrict__ bias,
@@ -208,8 +224,9 @@ __global__ __launch_bounds__(256) void wdl_head_kernel(int B, int Fw, int H, con
                                                        float* __restrict__ z_out, float* __restrict__ dz,
                                                        void* __restrict__ dh_out, long long* __restrict__ g_w,
                                                        uint8_t* __restrict__ touched, float* __restrict__ slab,
-                                                       int32_t* err) {
+                                                       int32_t* err, HeadWeight sw) {
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const float inv_norm = WEIGHTED ? sw.norm[0] : 0.f;
   const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   const int nwaves = (gridDim.x * blockDim.x) >> 6;
   const int H4 = (H + 3) / 4;
@@ -266,13 +283,16 @@ __global__ __launch_bounds__(256) void wdl_head_kernel(int B, int Fw, int H, con
     const float z = wave_sum(part) + b0;
     const float p = 1.f / (1.f + expf(-z));
     const float y = label[b];
-    const float g = (-y / (p + eps) + (1.f - y) / (1.f - p + eps)) * inv_batch * p * (1.f - p);
+    const float wb = WEIGHTED ? sw.w_eff[b] : 1.f;
+    const float scale = WEIGHTED ? wb * inv_norm : inv_batch;
+    const float g = (-y / (p + eps) + (1.f - y) / (1.f - p + eps)) * scale * p * (1.f - p);
     if (lane == 0) {
       score[b] = p;
       if (z_out) z_out[b] = z;
       dz[b] = g;
       gb += g;
-      lsum += -y * logf(p + eps) - (1.f - y) * logf(1.f - p + eps);
+      const float l = -y * logf(p + eps) - (1.f - y) * logf(1.f - p + eps);
+      lsum += WEIGHTED ? wb * l : l;
     }
     if (wr >= 0 && g_w) {
       atomicAdd(reinterpret_cast<unsigned long long*>(g_w + wr), (unsigned long long)wide_fixed(g));
@@ -350,11 +370,12 @@ __global__ __launch_bounds__(256) void slab_fold_rows_kernel(const float* __rest
 
 using namespace dl;
 
-template <bool DHB>
+template <bool DHB, bool WEIGHTED = false>
 static int wdl_head(int32_t B, int32_t Fw, int32_t H, const int64_t* wide, int32_t wide_ld, const float* h,
                     int32_t ldh, const float* w, const float* bias, int64_t w_rows, const float* label, float eps,
                     float inv_batch, float* score, float* z_out, float* dz, void* dh, int64_t* g_w, uint8_t* touched,
-                    float* slab, int32_t slab_blocks, int32_t* err, void* stream) {
+                    float* slab, int32_t slab_blocks, int32_t* err, void* stream, HeadWeight sw = HeadWeight{}) {
+  DL_CHECK_ARG(!WEIGHTED || (sw.w_eff && sw.norm), "w_eff and norm required");
   DL_CHECK_ARG(Fw >= 0 && Fw <= 64, "Fw %d not in [0, 64]", Fw);
   DL_CHECK_ARG(H > 0 && H <= 4 * 64 * kHeadMaxH4, "H %d too large", H);
   DL_CHECK_ARG(w_rows >= Fw + H, "wdl_weights must have >= Fw + H rows");
@@ -365,12 +386,32 @@ static int wdl_head(int32_t B, int32_t Fw, int32_t H, const int64_t* wide, int32
   DL_CHECK_ARG(slab_blocks >= grid, "slab needs %d blocks", grid);
   if (B == 0) return 0;
   const size_t lds = 4 * (size_t)(H + 2) * sizeof(float);
-  auto kern = H <= 4 * 64 * 2 ? wdl_head_kernel<DHB, 2> : wdl_head_kernel<DHB, kHeadMaxH4>;
+  auto kern = H <= 4 * 64 * 2 ? wdl_head_kernel<DHB, 2, WEIGHTED> : wdl_head_kernel<DHB, kHeadMaxH4, WEIGHTED>;
   hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, as_stream(stream), B, Fw, H, wide, wide_ld,
                      h, ldh, w, bias, (long long)w_rows, label, eps, inv_batch, score, z_out, dz, dh,
                      reinterpret_cast<long long*>(g_w), touched,
-                     slab, err);
+                     slab, err, sw);
   DL_RETURN_LAUNCH(DHB ? "dl_wdl_head_fwd_bwd_bf16" : "dl_wdl_head_fwd_bwd");
+}
+
+extern "C" int dl_wdl_head_fwd_bwd_weighted(int32_t B, int32_t Fw, int32_t H, const int64_t* wide, int32_t wide_ld,
+                                            const float* h, int32_t ldh, const float* w, const float* bias,
+                                            int64_t w_rows, const float* label, float eps, const float* w_eff,
+                                            const float* norm, float* score, float* z_out, float* dz, float* dh,
+                                            int64_t* g_w, uint8_t* touched, float* slab, int32_t slab_blocks,
+                                            int32_t* err, void* stream) {
+  return wdl_head<false, true>(B, Fw, H, wide, wide_ld, h, ldh, w, bias, w_rows, label, eps, 0.f, score, z_out, dz,
+                               dh, g_w, touched, slab, slab_blocks, err, stream, HeadWeight{w_eff, norm});
+}
+
+extern "C" int dl_wdl_head_fwd_bwd_bf16_weighted(int32_t B, int32_t Fw, int32_t H, const int64_t* wide,
+                                                 int32_t wide_ld, const float* h, int32_t ldh, const float* w,
+                                                 const float* bias, int64_t w_rows, const float* label, float eps,
+                                                 const float* w_eff, const float* norm, float* score, float* z_out,
+                                                 float* dz, uint16_t* dh, int64_t* g_w, uint8_t* touched, float* slab,
+                                                 int32_t slab_blocks, int32_t* err, void* stream) {
+  return wdl_head<true, true>(B, Fw, H, wide, wide_ld, h, ldh, w, bias, w_rows, label, eps, 0.f, score, z_out, dz,
+                              dh, g_w, touched, slab, slab_blocks, err, stream, HeadWeight{w_eff, norm});
 }
 
 extern "C" int dl_wdl_head_fwd_bwd(int32_t B, int32_t Fw, int32_t H, const int64_t* wide, int32_t wide_ld,
@@ -415,22 +456,46 @@ extern "C" int dl_wdl_head_grid(int32_t B) {
   return g < 1 ? 1 : g;
 }
 
+// dl_head_fwd_bwd and its twins: DROP (FM-part dropout, dr) and WEIGHTED (sample weights, sw)
+template <bool DROP, bool WEIGHTED>
+static int head_launch(const char* name, int32_t B, int32_t fm_cols, int32_t H, const float* fm_out, int32_t fm_ld,
+                       const float* h, int32_t ldh, const float* w, const float* label, float eps, float inv_batch,
+                       float* score, float* z_out, float* dz, float* dh, float* slab, int32_t slab_blocks,
+                       const HeadDrop& dr, HeadWeight sw, void* stream) {
+  DL_CHECK_ARG(fm_cols >= (DROP ? 1 : 0) && fm_cols <= kHeadMaxFm, "fm_cols %d not in [%d, %d]", fm_cols,
+               DROP ? 1 : 0, kHeadMaxFm);
+  DL_CHECK_ARG(H > 0 && H <= 4 * 64 * kHeadMaxH4, "H %d > %d", H, 4 * 64 * kHeadMaxH4);
+  DL_CHECK_ARG(ldh % 4 == 0 && ldh >= H && ((uintptr_t)h % 16) == 0, "h must be 16-B aligned, ldh %% 4 == 0");
+  DL_CHECK_ARG(!fm_cols || fm_out, "fm_out required");
+  DL_CHECK_ARG(!WEIGHTED || (sw.w_eff && sw.norm), "w_eff and norm required");
+  if (DROP) {
+    DL_CHECK_ARG(dr.F >= 0 && dr.F <= fm_cols, "F %d not in [0, fm_cols %d]", dr.F, fm_cols);
+    DL_CHECK_ARG(dr.opt && dr.fm_keep && ((uintptr_t)dr.fm_keep % 16) == 0, "opt and a 16-B aligned fm_keep required");
+    DL_CHECK_ARG(dr.inv1 >= 1.f && dr.inv1 < 3.4e38f && dr.inv2 >= 1.f && dr.inv2 < 3.4e38f,
+                 "bad dropout factors %g %g", (double)dr.inv1, (double)dr.inv2);
+  }
+  const int grid = dl_head_grid(B);
+  DL_CHECK_ARG(slab_blocks >= grid, "slab needs %d blocks", grid);
+  if (B == 0) return 0;
+  const size_t lds = 4 * (size_t)(fm_cols + H + 2) * sizeof(float);
+  hipLaunchKernelGGL((head_kernel<DROP, WEIGHTED>), dim3(grid), dim3(256), lds, as_stream(stream), B, fm_cols, H,
+                     fm_out, fm_ld, h, ldh, w, label, eps, inv_batch, score, z_out, dz, dh, slab, dr, sw);
+  DL_RETURN_LAUNCH(name);
+}
+
+static HeadDrop head_drop(int32_t F, uint32_t keep_thr1, float inv1, uint32_t keep_thr2, float inv2, uint64_t seed,
+                          const float* opt, uint64_t* fm_keep) {
+  return HeadDrop{F, keep_thr1, keep_thr2, inv1, inv2, make_uint2((uint32_t)seed, (uint32_t)(seed >> 32)), opt,
+                  reinterpret_cast<unsigned long long*>(fm_keep)};
+}
+
 extern "C" int dl_head_fwd_bwd(int32_t B, int32_t fm_cols, int32_t H, const float* fm_out,
                                int32_t fm_ld, const float* h, int32_t ldh, const float* w,
                                const float* label, float eps, float inv_batch, float* score,
                                float* z_out, float* dz, float* dh, float* slab,
                                int32_t slab_blocks, void* stream) {
-  DL_CHECK_ARG(fm_cols >= 0 && fm_cols <= kHeadMaxFm, "fm_cols %d > %d", fm_cols, kHeadMaxFm);
-  DL_CHECK_ARG(H > 0 && H <= 4 * 64 * kHeadMaxH4, "H %d > %d", H, 4 * 64 * kHeadMaxH4);
-  DL_CHECK_ARG(ldh % 4 == 0 && ldh >= H && ((uintptr_t)h % 16) == 0, "h must be 16-B aligned, ldh %% 4 == 0");
-  DL_CHECK_ARG(!fm_cols || fm_out, "fm_out required");
-  const int grid = dl_head_grid(B);
-  DL_CHECK_ARG(slab_blocks >= grid, "slab needs %d blocks", grid);
-  if (B == 0) return 0;
-  const size_t lds = 4 * (size_t)(fm_cols + H + 2) * sizeof(float);
-  hipLaunchKernelGGL(head_kernel<false>, dim3(grid), dim3(256), lds, as_stream(stream), B, fm_cols, H,
-                     fm_out, fm_ld, h, ldh, w, label, eps, inv_batch, score, z_out, dz, dh, slab, HeadDrop{});
-  DL_RETURN_LAUNCH("dl_head_fwd_bwd");
+  return head_launch<false, false>("dl_head_fwd_bwd", B, fm_cols, H, fm_out, fm_ld, h, ldh, w, label, eps, inv_batch,
+                                   score, z_out, dz, dh, slab, slab_blocks, HeadDrop{}, HeadWeight{}, stream);
 }
 
 extern "C" int dl_head_fwd_bwd_fmdrop(int32_t B, int32_t fm_cols, int32_t H, const float* fm_out, int32_t fm_ld,
@@ -439,20 +504,30 @@ extern "C" int dl_head_fwd_bwd_fmdrop(int32_t B, int32_t fm_cols, int32_t H, con
                                       int32_t slab_blocks, int32_t F, uint32_t keep_thr1, float inv1,
                                       uint32_t keep_thr2, float inv2, uint64_t seed, const float* opt,
                                       uint64_t* fm_keep, void* stream) {
-  DL_CHECK_ARG(fm_cols > 0 && fm_cols <= kHeadMaxFm, "fm_cols %d not in [1, %d]", fm_cols, kHeadMaxFm);
-  DL_CHECK_ARG(F >= 0 && F <= fm_cols, "F %d not in [0, fm_cols %d]", F, fm_cols);
-  DL_CHECK_ARG(H > 0 && H <= 4 * 64 * kHeadMaxH4, "H %d > %d", H, 4 * 64 * kHeadMaxH4);
-  DL_CHECK_ARG(ldh % 4 == 0 && ldh >= H && ((uintptr_t)h % 16) == 0, "h must be 16-B aligned, ldh %% 4 == 0");
-  DL_CHECK_ARG(fm_out && opt && fm_keep && ((uintptr_t)fm_keep % 16) == 0, "fm_out, opt and a 16-B aligned fm_keep required");
-  DL_CHECK_ARG(inv1 >= 1.f && inv1 < 3.4e38f && inv2 >= 1.f && inv2 < 3.4e38f, "bad dropout factors %g %g",
-               (double)inv1, (double)inv2);
-  const int grid = dl_head_grid(B);
-  DL_CHECK_ARG(slab_blocks >= grid, "slab needs %d blocks", grid);
-  if (B == 0) return 0;
-  const size_t lds = 4 * (size_t)(fm_cols + H + 2) * sizeof(float);
-  const HeadDrop dr{F, keep_thr1, keep_thr2, inv1, inv2, make_uint2((uint32_t)seed, (uint32_t)(seed >> 32)), opt,
-                    reinterpret_cast<unsigned long long*>(fm_keep)};
-  hipLaunchKernelGGL(head_kernel<true>, dim3(grid), dim3(256), lds, as_stream(stream), B, fm_cols, H,
-                     fm_out, fm_ld, h, ldh, w, label, eps, inv_batch, score, z_out, dz, dh, slab, dr);
-  DL_RETURN_LAUNCH("dl_head_fwd_bwd_fmdrop");
+  return head_launch<true, false>("dl_head_fwd_bwd_fmdrop", B, fm_cols, H, fm_out, fm_ld, h, ldh, w, label, eps,
+                                  inv_batch, score, z_out, dz, dh, slab, slab_blocks,
+                                  head_drop(F, keep_thr1, inv1, keep_thr2, inv2, seed, opt, fm_keep), HeadWeight{},
+                                  stream);
+}
+
+extern "C" int dl_head_fwd_bwd_weighted(int32_t B, int32_t fm_cols, int32_t H, const float* fm_out, int32_t fm_ld,
+                                        const float* h, int32_t ldh, const float* w, const float* label, float eps,
+                                        const float* w_eff, const float* norm, float* score, float* z_out, float* dz,
+                                        float* dh, float* slab, int32_t slab_blocks, void* stream) {
+  return head_launch<false, true>("dl_head_fwd_bwd_weighted", B, fm_cols, H, fm_out, fm_ld, h, ldh, w, label, eps,
+                                  0.f, score, z_out, dz, dh, slab, slab_blocks, HeadDrop{}, HeadWeight{w_eff, norm},
+                                  stream);
+}
+
+extern "C" int dl_head_fwd_bwd_fmdrop_weighted(int32_t B, int32_t fm_cols, int32_t H, const float* fm_out,
+                                               int32_t fm_ld, const float* h, int32_t ldh, const float* w,
+                                               const float* label, float eps, const float* w_eff, const float* norm,
+                                               float* score, float* z_out, float* dz, float* dh, float* slab,
+                                               int32_t slab_blocks, int32_t F, uint32_t keep_thr1, float inv1,
+                                               uint32_t keep_thr2, float inv2, uint64_t seed, const float* opt,
+                                               uint64_t* fm_keep, void* stream) {
+  return head_launch<true, true>("dl_head_fwd_bwd_fmdrop_weighted", B, fm_cols, H, fm_out, fm_ld, h, ldh, w, label,
+                                 eps, 0.f, score, z_out, dz, dh, slab, slab_blocks,
+                                 head_drop(F, keep_thr1, inv1, keep_thr2, inv2, seed, opt, fm_keep),
+                                 HeadWeight{w_eff, norm}, stream);
 }

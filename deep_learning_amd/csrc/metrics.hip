@@ -502,6 +502,50 @@ __global__ __launch_bounds__(kScanThreads) void stats_final_kernel(const double*
   }
 }
 
+// dl_eval_stats_weighted: the same two stages over five sums {w l, w p, w y, w, [w != 0]}.  A
+// weight outside [0, inf) enters as NaN, so the four weighted sums come out NaN.
+constexpr int kWStats = 5;
+
+__global__ __launch_bounds__(kScanThreads) void wstats_partial_kernel(const float* __restrict__ scores, int64_t s_stride,
+                                                                      const float* __restrict__ labels, int64_t l_stride,
+                                                                      const float* __restrict__ weights,
+                                                                      int64_t w_stride, long long n, double eps,
+                                                                      double* __restrict__ part) {
+  __shared__ double shd[kScanThreads / 64];
+  double v[kWStats] = {};
+  for (long long i = (long long)blockIdx.x * kScanThreads + threadIdx.x; i < n;
+       i += (long long)gridDim.x * kScanThreads) {
+    const double p = (double)scores[i * s_stride];
+    const bool y = labels[i * l_stride] > 0.5f;
+    const float wf = weights[i * w_stride];
+    const double w = (wf >= 0.f && wf <= 3.402823466e38f) ? (double)wf : __longlong_as_double(0x7ff8000000000000ll);
+    v[0] += w * (y ? -log(p + eps) : -log(1.0 - p + eps));
+    v[1] += w * p;
+    v[2] += y ? w : 0.0;
+    v[3] += w;
+    v[4] += wf != 0.f ? 1.0 : 0.0;
+  }
+#pragma unroll
+  for (int k = 0; k < kWStats; ++k) {
+    const double t = block_sum_f64(v[k], shd);
+    if (threadIdx.x == 0) part[kWStats * blockIdx.x + k] = t;
+  }
+}
+
+__global__ __launch_bounds__(kScanThreads) void wstats_final_kernel(const double* __restrict__ part, int blocks,
+                                                                    double* __restrict__ out) {
+  __shared__ double shd[kScanThreads / 64];
+  double v[kWStats] = {};
+  for (int b = threadIdx.x; b < blocks; b += kScanThreads)
+#pragma unroll
+    for (int k = 0; k < kWStats; ++k) v[k] += part[kWStats * b + k];
+#pragma unroll
+  for (int k = 0; k < kWStats; ++k) {
+    const double t = block_sum_f64(v[k], shd);
+    if (threadIdx.x == 0) out[k] = t;
+  }
+}
+
 }  // namespace
 }  // namespace dl
 
@@ -614,6 +658,28 @@ extern "C" int dl_eval_stats(const float* scores, int64_t s_stride, const float*
                      (long long)n, eps, part);
   hipLaunchKernelGGL(stats_final_kernel, dim3(1), dim3(kScanThreads), 0, s, part, blocks, (long long)n, out);
   DL_RETURN_LAUNCH("dl_eval_stats");
+}
+
+extern "C" int64_t dl_eval_stats_weighted_workspace_bytes(int64_t n) {
+  if (n <= 0 || n > 0x7fffffff) return -1;
+  return 8ll * kWStats * stats_blocks(n);
+}
+
+extern "C" int dl_eval_stats_weighted(const float* scores, int64_t s_stride, const float* labels, int64_t l_stride,
+                                      const float* weights, int64_t w_stride, int64_t n, double eps, void* ws,
+                                      int64_t ws_bytes_, double* out, void* stream) {
+  DL_CHECK_ARG(scores && labels && weights && out && ws, "NULL argument");
+  DL_CHECK_ARG(n > 0 && n <= 0x7fffffff, "n = %lld out of range", (long long)n);
+  DL_CHECK_ARG(((uintptr_t)ws & 7) == 0, "workspace not 8-B aligned");
+  DL_CHECK_ARG(ws_bytes_ >= dl_eval_stats_weighted_workspace_bytes(n), "workspace too small (%lld < %lld)",
+               (long long)ws_bytes_, (long long)dl_eval_stats_weighted_workspace_bytes(n));
+  hipStream_t s = as_stream(stream);
+  const int blocks = stats_blocks(n);
+  double* part = static_cast<double*>(ws);
+  hipLaunchKernelGGL(wstats_partial_kernel, dim3(blocks), dim3(kScanThreads), 0, s, scores, s_stride, labels,
+                     l_stride, weights, w_stride, (long long)n, eps, part);
+  hipLaunchKernelGGL(wstats_final_kernel, dim3(1), dim3(kScanThreads), 0, s, part, blocks, out);
+  DL_RETURN_LAUNCH("dl_eval_stats_weighted");
 }
 
 // ---------------------------------------------------------------------------

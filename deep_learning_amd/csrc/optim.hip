@@ -36,7 +36,9 @@ __global__ void adam_begin_kernel(float* opt, float decay_rate, float decay_step
 __device__ __forceinline__ void step_guard_kernel_body(const int32_t* batch_err, float* opt) {
   const int e = batch_err[0];
   int* st = opt_status(opt);
-  const int bad = e ? ((e & DL_STATUS_BAD_ID) ? DL_STATUS_BAD_ID : e) : 0;
+  // the batch's own bits: a bad id and / or a bad sample weight (dl_weight_norm), else the word as it is
+  constexpr int kBatchBits = DL_STATUS_BAD_ID | DL_STATUS_BAD_WEIGHT;
+  const int bad = e ? ((e & kBatchBits) ? (e & kBatchBits) : e) : 0;
   // this step's skip word: the batch's own bits + any sticky internal fault
   st[DL_OPT_SKIP - DL_OPT_STATUS] = bad | (st[0] & kStickyFaults);
   if (bad) {

@@ -78,14 +78,22 @@ class ModelSpec:
     first-order products and on the second-order vector, deepfm_pipeline.py:98,110): two values in
     (0, 1], a longer list truncated; None, with no effect, for all ones and for the models without
     an FM part (dnn*, wdl), whose reference classes never read it.
+    pos_weight: the loss weight of a positive sample relative to a negative one (finite, > 0;
+    tf.losses.log_loss's weights= with w_b = weight_b * (1 + (pos_weight - 1) * y_b), which the
+    reference leaves at 1); anything but 1 turns the engine's sample weighting on
+    (CTREngine(sample_weight=...)).
     """
 
     def __init__(self, model, C=13, V=0, S=26, E=16, cate_index_size=1000, hidden=(400, 400, 400),
                  multi_ranges=(), Fw=0, lr=0.001, l2=1e-5, decay_steps=10000000, decay_rate=0.9,
                  beta1=0.9, beta2=0.999, eps=1e-8, logloss_eps=1e-7, tower="f32", dropout_keep_deep=None,
-                 dropout_keep_fm=None):
+                 dropout_keep_fm=None, pos_weight=1.0):
         if model not in FAMILIES:
             raise ValueError("unsupported model %r" % model)
+        pos_weight = float(pos_weight)
+        if not (math.isfinite(pos_weight) and pos_weight > 0.0):
+            raise ValueError("pos_weight must be finite and > 0, got %r" % (pos_weight,))
+        self.pos_weight = pos_weight
         fam = FAMILIES[model]
         self.model = model
         self.cont_mode = fam["cont"]
@@ -257,7 +265,13 @@ def _v_to_root(v):
 class CTREngine:
     def __init__(self, spec, max_batch, device="cuda", seed=2019, init="device", bwd="atomic",
                  table_rows=None, adam="dense", hist_len=4096, rec_stash=True, fwd_rec=False, gemm="s3",
-                 fwd_scatter=None):
+                 fwd_scatter=None, sample_weight=False):
+        # sample weights (tf.losses.log_loss's weights=): on with sample_weight (the
+        # batch's "weight" entry) or with ModelSpec.pos_weight != 1
+        self.weighted = bool(sample_weight) or spec.pos_weight != 1.0
+        if self.weighted and type(self) is not CTREngine:
+            raise ValueError("sample_weight / pos_weight: not supported by %s (the loss normaliser, the batch's "
+                             "nonzero-weight count, would need an all-reduce across the ranks)" % type(self).__name__)
         if not torch.cuda.is_available():
             raise _lib.DLError("CTREngine needs a HIP device (no CPU fallback)")
         _lib.lib()
@@ -570,6 +584,10 @@ class CTREngine:
         self.in_cont = z(B, max(sp.C, 1))
         self.in_vec = z(B, max(sp.V, 1))
         self.in_cate = z(B, max(sp.cate_ld, 1), dt=torch.int64)
+        if self.weighted:
+            # the batch's weights, its effective weights and {inv_norm, N_nz} (dl_weight_norm, in _pre):
+            # per buffer set, as the labels they belong to
+            self.in_weight, self.w_eff, self.norm = z(B), z(B), z(4)
         self.graphs = {}        # (buffer set, batch) -> captured step
         # predict on a flushed table reads dense p / first-order planes written by the flush
         # (DLAMD_FLAT_PLANES=0: each reference reads its record's first line instead)
@@ -995,6 +1013,15 @@ class CTREngine:
         _copy_in(self.in_cate[:B, : sp.cate_ld], batch["cate_feats"], torch.int64, self.dev)
         if sp.Fw:
             _copy_in(self.in_wide[:B, : sp.Fw], batch["wide_feats"], torch.int64, self.dev)
+        if self.weighted:
+            w = batch.get("weight")
+            if w is None:
+                self.in_weight[:B].fill_(1.0)
+            else:
+                n = int(np.prod(np.shape(w)))
+                if n != B:
+                    raise ValueError("batch weight holds %d values for %d labels" % (n, B))
+                _copy_in(self.in_weight[:B], w, F32, self.dev)
         return B
 
     # ------------------------------------------------------------------ step
@@ -1179,6 +1206,9 @@ class CTREngine:
                         ptr(self.W[l]), self.out_ld[l], ptr(self.h[l]), self.h_ld[l], 1, None, 0, 1, 0, s)
                 x = self.h[l]
         H = sp.hidden[-1]
+        # the loss scale: the host constant 1 / B, or in a weighted training step the *_weighted
+        # twins' (w_eff, norm) — predict ignores the weights
+        sw, scale = ("_weighted", (ptr(self.w_eff), ptr(self.norm))) if train and self.weighted else ("", (1.0 / B,))
         if self.wdl and self.wide_lazy:
             # the batch's wide rows caught up into the compact local table, the head on local ids
             fn, dh_last = ("dl_wdl_head_fwd_bwd_bf16", self.dhb[-1]) if self.bf else ("dl_wdl_head_fwd_bwd", self.dh[-1])
@@ -1187,8 +1217,8 @@ class CTREngine:
                     ptr(self.widx_n), nw, sp.Fw, H, ptr(self.hist), self.hist_len, ptr(self.opt), sp.l2,
                     1 if train else 0, ptr(self.wloc), ptr(self.wstash) if train else None,
                     ptr(self.wrep) if train else None, s)
-            self._c("head", fn, B, sp.Fw, H, ptr(self.in_wide_loc), sp.Fw, ptr(self.h[-1]), self.h_ld[-1],
-                    ptr(self.wloc), ptr(self.wb), sp.Fw + H + nw, ptr(self.in_label), sp.logloss_eps, 1.0 / B,
+            self._c("head", fn + sw, B, sp.Fw, H, ptr(self.in_wide_loc), sp.Fw, ptr(self.h[-1]), self.h_ld[-1],
+                    ptr(self.wloc), ptr(self.wb), sp.Fw + H + nw, ptr(self.in_label), sp.logloss_eps, *scale,
                     ptr(self.score), ptr(self.z), ptr(self.dz), ptr(dh_last), None, None,
                     ptr(self.head_slab), self.head_blocks, ptr(self.err), s)
             if train:   # the wide rows' gradient: segment sums over the wide index (no atomics)
@@ -1198,32 +1228,34 @@ class CTREngine:
         if self.wdl:
             # bf16 tower: dY of the last layer written as bf16 by the head itself (no cast pass)
             fn, dh_last = ("dl_wdl_head_fwd_bwd_bf16", self.dhb[-1]) if self.bf else ("dl_wdl_head_fwd_bwd", self.dh[-1])
-            self._c("head", fn, B, sp.Fw, H, ptr(self.in_wide), self.in_wide.shape[1],
+            self._c("head", fn + sw, B, sp.Fw, H, ptr(self.in_wide), self.in_wide.shape[1],
                     ptr(self.h[-1]), self.h_ld[-1], ptr(self.ww), ptr(self.wb), self.w_rows, ptr(self.in_label),
-                    sp.logloss_eps, 1.0 / B, ptr(self.score), ptr(self.z), ptr(self.dz), ptr(dh_last),
+                    sp.logloss_eps, *scale, ptr(self.score), ptr(self.z), ptr(self.dz), ptr(dh_last),
                     ptr(self.wg) if train else None, ptr(self.w_touched) if train else None,
                     ptr(self.head_slab), self.head_blocks, ptr(self.err), s)
             return
         if train and self.fmdrop:   # predict / evaluate never drop
             k1, k2 = self.fmdrop
-            self._c("head", "dl_head_fwd_bwd_fmdrop", B, sp.fm_cols, H, ptr(self.fm_out), self.fm_ld, ptr(self.h[-1]),
-                    self.h_ld[-1], ptr(self.w_head), ptr(self.in_label), sp.logloss_eps, 1.0 / B,
+            self._c("head", "dl_head_fwd_bwd_fmdrop" + sw, B, sp.fm_cols, H, ptr(self.fm_out), self.fm_ld,
+                    ptr(self.h[-1]), self.h_ld[-1], ptr(self.w_head), ptr(self.in_label), sp.logloss_eps, *scale,
                     ptr(self.score), ptr(self.z), ptr(self.dz), ptr(self.dh[-1]), ptr(self.head_slab),
                     self.head_blocks, sp.F, self._keep_thr(k1), self._keep_inv(k1), self._keep_thr(k2),
                     self._keep_inv(k2), self.seed & 0xFFFFFFFFFFFFFFFF, ptr(self.opt), ptr(self.fm_keep), s)
             return
-        self._c("head", "dl_head_fwd_bwd", B, sp.fm_cols, H, ptr(self.fm_out), self.fm_ld, ptr(self.h[-1]),
-             self.h_ld[-1], ptr(self.w_head), ptr(self.in_label), sp.logloss_eps, 1.0 / B,
+        self._c("head", "dl_head_fwd_bwd" + sw, B, sp.fm_cols, H, ptr(self.fm_out), self.fm_ld, ptr(self.h[-1]),
+             self.h_ld[-1], ptr(self.w_head), ptr(self.in_label), sp.logloss_eps, *scale,
              ptr(self.score), ptr(self.z), ptr(self.dz), ptr(self.dh[-1]), ptr(self.head_slab),
              self.head_blocks, s)
 
-    def _pre(self, B):
+    def _pre(self, B, weights=True):
         """The batch's validation and index build, before its step begins: the batch's
         validation word is reset, then set by dl_validate_batch for every id no index build
         checks (the dense-layout gathers' cate ids, wdl's wide ids) and by dl_index_build (the
         hand-written radix sort + segmented unique of index.hip, no host synchronisation).
         Runs on the current stream — inside the step's hipGraph (graph=True), or on the side
-        stream when prefetched — so a bad batch is known before dl_step_begin opens its step."""
+        stream when prefetched — so a bad batch is known before dl_step_begin opens its step.
+        With sample weighting (and `weights`: a training batch) dl_weight_norm follows the
+        validation: the effective weights, the loss normaliser and the bad-weight bit."""
         s = _lib.stream_handle()
         L = self.layout
         L.batch = B
@@ -1232,6 +1264,9 @@ class CTREngine:
         wide = self.in_wide if self.wdl else None
         self._c("validate", "dl_validate_batch", C_ref(L), ptr(cate), ptr(wide), sp.Fw if wide is not None else 0,
                 self.in_wide.shape[1], getattr(self, "w_rows", 0), 1, ptr(self.err), s)
+        if self.weighted and weights:
+            self._c("weight_norm", "dl_weight_norm", ptr(self.in_weight), ptr(self.in_label), B, sp.pos_weight,
+                    ptr(self.w_eff), ptr(self.norm), ptr(self.err), s)
         if self.bwd != "sorted":
             return
         if self.index_pair:
@@ -1269,6 +1304,11 @@ class CTREngine:
         sp = self.spec
         width = self.head_slab.shape[1]
         coef = sp.l2 if sp.hidden_reg == "l1" else 0.5 * sp.l2
+        if self.weighted:
+            self._c("loss_acc", "dl_loss_accumulate_weighted", ptr(self.head_slab), call_int(self.head_grid, B), width,
+                    width - 1, ptr(self.norm), ptr(self.opt), coef, ptr(self.loss_acc), ptr(self._ring),
+                    _lib.stream_handle())
+            return
         self._c("loss_acc", "dl_loss_accumulate", ptr(self.head_slab), call_int(self.head_grid, B), width, width - 1,
                 1.0 / B, ptr(self.opt), coef, ptr(self.loss_acc), ptr(self._ring), _lib.stream_handle())
 
@@ -1485,7 +1525,7 @@ class CTREngine:
     # while the current step runs.
     SLOT_ATTRS = ("in_label", "in_cont", "in_vec", "in_cate", "in_wide", "idx_ws", "idx_keys", "idx_refs",
                   "idx_uniq", "idx_off", "idx_n", "idx_inv", "err", "widx_ws", "widx_keys", "widx_refs", "widx_uniq",
-                  "widx_off", "widx_n", "winv", "in_wide_loc")
+                  "widx_off", "widx_n", "winv", "in_wide_loc", "in_weight", "w_eff", "norm")
 
     def _side_stream(self):
         if getattr(self, "side", None) is None:
@@ -1708,7 +1748,7 @@ class CTREngine:
         B, indexed = self._begin(batch)
         s = _lib.stream_handle()
         if not indexed:
-            self._pre(B)
+            self._pre(B, weights=False)
         self._forward(B, s)
         self._release()
         self.check_error()
@@ -1723,7 +1763,12 @@ class CTREngine:
         B = self.last_batch
         width = self.head_slab.shape[1]
         rows = call_int(self.head_grid, B)
-        data = self.head_slab[:rows, width - 1].double().sum().item() / B
+        data = self.head_slab[:rows, width - 1].double().sum().item()
+        if self.weighted:   # sum w l / N_nz (0 when every weight is 0), N_nz from the device normaliser
+            nz = float(self.norm[1].item())
+            data = data / nz if nz else 0.0
+        else:
+            data = data / B
         if sp.hidden_reg == "l1":   # l1_regularizer: scale * sum |W| (dnn.py:88-90)
             return data + sp.l2 * _lib.reg_sum(self.opt)
         reg = _lib.reg_sum(self.opt)
@@ -1850,7 +1895,8 @@ class CTREngine:
         # (predict); a trained batch's word is consumed by its step (dl_step_begin -> status),
         # and every batch's own validation resets its word (no other set's word is touched:
         # a prefetched bad batch must still be skipped by its own step)
-        bad = int(self.err[0].item()) != 0 and not status
+        errw = int(self.err[0].item())
+        bad = errw != 0 and not status
         if not status and not bad:
             return
         bad_step, n_bad = (int(x) for x in self.opt[_lib.OPT_BAD_STEP:_lib.OPT_BAD_COUNT + 1].tolist())
@@ -1862,6 +1908,12 @@ class CTREngine:
             raise _lib.DLError("internal: a row record lagged past the alpha ring (flush schedule)")
         if status & _lib.STATUS_INDEX:
             raise _lib.DLError("internal: batch index entry out of range (corrupt index)")
+        if (status or errw) & _lib.STATUS_BAD_WEIGHT and not (status or errw) & _lib.STATUS_BAD_ID:
+            raise _lib.DLError("InvalidArgumentError: sample weight negative, NaN or infinite (batch[\"weight\"] "
+                               "must be finite and >= 0) — %s" % (
+                                   "%d batch(es) skipped with no update, the last at global_step %d; the batches "
+                                   "around them applied normally" % (n_bad, bad_step) if status else
+                                   "in the current batch, no update applied"))
         if not status:   # a validated batch whose step has not begun yet (predict, or queued)
             raise _lib.DLError("InvalidArgumentError: categorical id out of range [0, %d) in the current "
                                "batch — no update applied" % self.N)

@@ -9,6 +9,10 @@ hard-codes (batch_size, hidden_units=400,400,400, learning_rate, l2_reg,
 learning_rate_decay_steps/_rate, dropout_keep_deep=1,0.8,0.8,0.8, dropout_keep_fm=0.9,0.8, shuffle=0|1, shuffle_seed=N), so the
 BASELINE configs (batch 65536, MLP [400]*3) are reachable from the same CLI.
 
+pos_weight=2.5 weights the positives' loss terms and weight_key=NAME reads a per-sample loss weight
+from the float [1] TFRecord feature NAME (tf.losses.log_loss's weights=, which the reference leaves
+at 1); with weight_key, evaluation's logloss and calibration are weighted too.
+
 Two more overrides choose what evaluation reports (deep_learning_amd/metrics.py); without them
 the output is the reference's: eval_metrics=auc,gauc,logloss,calibration (default auc) and
 gauc_slot=K, the cate_feats column whose id groups the samples for GAUC (the user-id slot).
@@ -63,6 +67,12 @@ class ModelParams:
                 self.gauc_slot = int(v)
             elif k == "eval_metrics":
                 self.eval_metrics = [m for m in v.split(",") if m]
+            elif k == "pos_weight":     # sample weighting, stored only when given as well
+                self.pos_weight = check_pos_weight(v)
+            elif k == "weight_key":
+                if not v:
+                    raise SystemExit("weight_key= needs the name of a float [1] TFRecord feature")
+                self.weight_key = v
             else:
                 raise SystemExit("unknown override %s" % k)
         (self.cont_field_size, self.vector_feats_size, self.cate_field_size, self.multi_feats_size,
@@ -71,6 +81,17 @@ class ModelParams:
 
 
 EVAL_METRICS = ("auc", "gauc", "logloss", "calibration")
+
+
+def check_pos_weight(v):
+    """pos_weight=V as a float; refuses (SystemExit) anything not finite and > 0."""
+    try:
+        w = float(v)
+    except ValueError:
+        raise SystemExit("pos_weight=%s is not a number" % v)
+    if not (w > 0.0 and w != float("inf")):
+        raise SystemExit("pos_weight=%s must be finite and > 0" % v)
+    return w
 
 
 def check_eval_options(eval_metrics, gauc_slot, cate_field_size):

@@ -111,15 +111,39 @@ def _gauc_call(labels, scores, groups, weighting):
     return v, int(covered), int(valid), int(total)
 
 
-def eval_stats(labels, scores, eps=1e-7):
+def eval_stats(labels, scores, eps=1e-7, weights=None):
     """Log-loss (the reference's eps form, in double), calibration (sum of scores / positives),
-    mean score, positive rate and n of scores against 0/1 labels."""
+    mean score, positive rate and n of scores against 0/1 labels.
+
+    weights (per sample, finite and >= 0; ``dl_eval_stats_weighted``): log-loss = sum w l / sum w,
+    calibration = sum w p / sum w y, mean score = sum w p / sum w, positive rate = sum w y / sum w.
+    This is the population estimate — the statistics of the traffic a down-sampled or
+    importance-weighted set stands for — and not the training loss's normaliser (which divides
+    by the count of nonzero weights, tf.losses.log_loss's SUM_BY_NONZERO_WEIGHTS).  ``n`` stays the
+    sample count; ``weight_sum`` and ``n_nonzero`` are added.  A zero total weight gives NaN
+    statistics.  All-ones weights give the unweighted values."""
     (s, ss), (y, ys) = _strided_f32(scores), _strided_f32(labels)
     n = s.numel()
     if y.numel() != n:
         raise ValueError("labels and scores differ in length")
     if n == 0:
         raise ValueError("no samples")
+    if weights is not None:
+        w, wst = _strided_f32(weights)
+        if w.numel() != n:
+            raise ValueError("labels, scores and weights differ in length")
+        ws = torch.empty(int(_lib.lib().dl_eval_stats_weighted_workspace_bytes(n)) // 8, dtype=torch.float64,
+                         device="cuda")
+        out = torch.empty(5, dtype=torch.float64, device="cuda")
+        call("dl_eval_stats_weighted", ptr(s), ss, ptr(y), ys, ptr(w), wst, n, float(eps), ptr(ws), ws.numel() * 8,
+             ptr(out), _lib.stream_handle())
+        loss, sp, sy, sw, nz = out.tolist()
+        if sw != sw:
+            raise ValueError("weights must be finite and >= 0")
+        nan = float("nan")
+        cal = sp / sy if sy else (float("inf") if sp > 0 else nan)
+        return {"logloss": loss / sw if sw else nan, "calibration": cal, "mean_score": sp / sw if sw else nan,
+                "positive_rate": sy / sw if sw else nan, "n": n, "weight_sum": sw, "n_nonzero": int(nz)}
     ws = torch.empty(int(_lib.lib().dl_eval_stats_workspace_bytes(n)) // 8, dtype=torch.float64, device="cuda")
     out = torch.empty(4, dtype=torch.float64, device="cuda")
     call("dl_eval_stats", ptr(s), ss, ptr(y), ys, n, float(eps), ptr(ws), ws.numel() * 8, ptr(out),
@@ -138,10 +162,20 @@ class EvalAccumulator(AucAccumulator):
     def __init__(self, weighting="size"):
         super().__init__()
         self.groups = []
+        self.weights = []
         self.weighting = weighting
 
-    def add(self, labels, scores, groups=None):
+    def add(self, labels, scores, groups=None, weights=None):
+        """weights: per-sample weights of log-loss and calibration (eval_stats), for every batch
+        or for none; AUC and GAUC stay unweighted."""
         super().add(labels, scores)
+        if (weights is None) != (not self.weights) and len(self.scores) > 1:
+            raise ValueError("weights must be given for every batch or for none")
+        if weights is not None:
+            w = _dev_f32(weights)
+            if w.numel() != self.scores[-1].numel():
+                raise ValueError("labels, scores and weights differ in length")
+            self.weights.append(w)
         if (groups is None) != (not self.groups) and len(self.scores) > 1:
             raise ValueError("groups must be given for every batch or for none")
         if groups is not None:
@@ -154,7 +188,7 @@ class EvalAccumulator(AucAccumulator):
         if not self.scores:
             raise ValueError(_SINGLE_CLASS)
         y, s = torch.cat(self.labels), torch.cat(self.scores)
-        st = eval_stats(y, s)
+        st = eval_stats(y, s, weights=torch.cat(self.weights) if self.weights else None)
         out = {"auc": roc_auc(y, s), "logloss": st["logloss"], "calibration": st["calibration"]}
         if self.groups:
             v, d = group_auc(y, s, torch.cat(self.groups), weighting=self.weighting, details=True)

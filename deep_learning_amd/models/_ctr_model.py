@@ -50,6 +50,8 @@ def _spec_from_args(model, args):
     keep_fm = getattr(args, "dropout_keep_fm", None)
     if keep_fm is not None:   # the reference hard-codes [1, 1] in its model classes (deepfm_pipeline.py:31)
         kw.update(dropout_keep_fm=[float(k) for k in keep_fm])
+    if getattr(args, "pos_weight", None) is not None:   # local_run's pos_weight= (stored only when given)
+        kw.update(pos_weight=float(args.pos_weight))
     return ModelSpec(model, **kw)
 
 
@@ -70,6 +72,11 @@ def _group_ids(cate, slot):
     if not 0 <= slot < cate.shape[1]:
         raise ValueError("gauc_slot=%d outside [0, %d)" % (slot, cate.shape[1]))
     return cate[:, slot]
+
+
+def _wants_weights(extra):
+    """Evaluation's sample weights feed log-loss and calibration only (AUC and GAUC are unweighted)."""
+    return "logloss" in extra or "calibration" in extra
 
 
 def _extra_fields(extra, res, fmt, prefix):
@@ -100,8 +107,10 @@ class CTRModel:
         """Builds the engine (the reference builds the graph here): returns
         (loss_fn, train_fn, global_step_fn)."""
         if self.engine is None:
+            # weight_key= (local_run): the batches carry a "weight" entry, the loss's sample weights
             self.engine = CTREngine(self.spec, max_batch=self.batch_size, seed=self.random_seed,
-                                    adam=default_adam(self.spec))
+                                    adam=default_adam(self.spec),
+                                    sample_weight=bool(getattr(self.args, "weight_key", None)))
         eng = self.engine
         return (eng.loss, lambda batch, next_batch=None: eng.train_step(batch, graph=True, next_batch=next_batch),
                 lambda: eng.steps)
@@ -154,12 +163,15 @@ class CTRModel:
 
     @staticmethod
     def get_val_data(sess, data):
-        labels, cont, cate, vec = [], [], [], []
+        labels, cont, cate, vec, wts = [], [], [], [], []
         for b in data:
             labels.append(b["label"])
             cont.append(b.get("cont_feats"))
             cate.append(b["cate_feats"])
             vec.append(b.get("vector_feats"))
+            wts.append(b.get("weight"))
+        if any(w is not None for w in wts):   # weight_key=: a fifth list, the batches' sample weights
+            return [labels, cont, cate, vec, wts]
         return [labels, cont, cate, vec]
 
     def eval(self, sess, val_data):
@@ -174,10 +186,12 @@ class CTRModel:
             if val_data[3][i] is not None:
                 batch["vector_feats"] = val_data[3][i]
             scores = _predict_batches(self.engine, batch)
+            kw = {}
             if slot is not None:
-                acc.add(val_data[0][i], scores, _group_ids(val_data[2][i], slot))
-            else:
-                acc.add(val_data[0][i], scores)
+                kw.update(groups=_group_ids(val_data[2][i], slot))
+            if len(val_data) > 4 and _wants_weights(extra):
+                kw.update(weights=val_data[4][i])
+            acc.add(val_data[0][i], scores, **kw)
         if not extra:
             return acc.result()
         res = acc.results()
@@ -311,10 +325,12 @@ def predict(predict_data, model_pb, eval_metrics=None, gauc_slot=None):
     for b in predict_data:
         if eng is None:
             eng = load_model(model_pb, max_batch=np.asarray(b["label"]).shape[0])
+        kw = {}
         if slot is not None:
-            acc.add(b["label"], _predict_batches(eng, b), _group_ids(b["cate_feats"], slot))
-        else:
-            acc.add(b["label"], _predict_batches(eng, b))
+            kw.update(groups=_group_ids(b["cate_feats"], slot))
+        if _wants_weights(extra) and b.get("weight") is not None:
+            kw.update(weights=b["weight"])
+        acc.add(b["label"], _predict_batches(eng, b), **kw)
     print("-----------end of data_set-----------")
     res = acc.results() if extra else {"auc": acc.result()}
     auc = res["auc"]

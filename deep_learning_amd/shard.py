@@ -165,9 +165,12 @@ class ShardedCTREngine(CTREngine):
     SLACK = 0.10
 
     def __init__(self, spec, max_batch, exch, device="cuda", seed=2019, adam="dense", hist_len=4096,
-                 owner_update=None, slack=None, lag=2):
+                 owner_update=None, slack=None, lag=2, sample_weight=False):
         if spec.model not in ("deepfm_pipeline", "dnn_pipeline", "wdl"):
             raise ValueError("sharded path supports deepfm_pipeline / dnn_pipeline / wdl")
+        if sample_weight or spec.pos_weight != 1.0:
+            raise ValueError("sample_weight / pos_weight: not supported by ShardedCTREngine (the loss normaliser, "
+                             "the batch's nonzero-weight count, would need an all-reduce across the ranks)")
         if spec.dropout:
             raise ValueError("dropout_keep_deep: not supported by ShardedCTREngine (the mask is indexed by the "
                              "local row number; a sharded batch needs global rows)")

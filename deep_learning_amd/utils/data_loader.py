@@ -32,12 +32,19 @@ CATE_ALGS = ("deepfm_cate", "dnn_cate", "dnn_multi_cate", "deepfm_multi_cate")
 def _spec(mp):
     if mp.alg_name in CATE_ALGS:
         print("-----------tf_cate-----------")
-        return {"cate_feats": ("int64", mp.cate_field_size + mp.multi_feats_size),
+        spec = {"cate_feats": ("int64", mp.cate_field_size + mp.multi_feats_size),
                 "label": ("float", 1), "vector_feats": ("float", mp.vector_feats_size)}
-    print("-----------tf_pipeline-----------")
-    return {"label": ("float", 1), "cont_feats": ("float", mp.cont_field_size),
-            "vector_feats": ("float", mp.vector_feats_size),
-            "cate_feats": ("int64", mp.cate_field_size + mp.multi_feats_size)}
+    else:
+        print("-----------tf_pipeline-----------")
+        spec = {"label": ("float", 1), "cont_feats": ("float", mp.cont_field_size),
+                "vector_feats": ("float", mp.vector_feats_size),
+                "cate_feats": ("int64", mp.cate_field_size + mp.multi_feats_size)}
+    wk = getattr(mp, "weight_key", None)
+    if wk:   # the per-sample loss weight: a float [1] feature, only when asked for
+        if wk in spec:
+            raise ValueError("weight_key=%s names a feature the model already reads" % wk)
+        spec[wk] = ("float", 1)
+    return spec
 
 
 def parse_example(data, spec):
@@ -64,6 +71,7 @@ class BatchStream:
         self.files = list(files)
         self.repeat = int(mp.epochs) if action_type == "train" else 1
         self.spec = _spec(mp)
+        self.weight_key = getattr(mp, "weight_key", None)
         self.bsz = int(mp.batch_size)
         self.shuffle = int(getattr(mp, "shuffle", 1))
         self.seed = getattr(mp, "shuffle_seed", None)
@@ -75,7 +83,8 @@ class BatchStream:
         spec = [(k, kind, size) for k, (kind, size) in self.spec.items()]
         r = NativeReader(self.files, spec, self.bsz, repeat=self.repeat,
                          shuffle_buf=self.bsz * 10 if self.shuffle else 0,   # shuffle(bsz*10), :34
-                         seed=self.seed, threads=self.threads, depth=self.depth)
+                         seed=self.seed, threads=self.threads, depth=self.depth,
+                         rename={self.weight_key: "weight"} if self.weight_key else None)
         return DeviceBatches(r, self.device, self.depth) if self.device else r
 
 
@@ -105,5 +114,8 @@ def write_tfrecord_part(path, batch):
                  "vector_feats": ("float", batch.get("vector_feats", np.zeros((n, 0)))[i].reshape(-1).tolist())}
         if "cont_feats" in batch:
             feats["cont_feats"] = ("float", batch["cont_feats"][i].reshape(-1).tolist())
+        for k in batch:   # further float features (a sample-weight column), under their own names
+            if k not in ("label", "cate_feats", "vector_feats", "cont_feats"):
+                feats[k] = ("float", np.asarray(batch[k][i], np.float32).reshape(-1).tolist())
         recs.append(tfrecord.encode_example(feats))
     tfrecord.write_records(path, recs)

@@ -153,15 +153,17 @@ class NativeReader:
     """Iterator of batches: dict name -> array [batch, size] (float32 / int64).
 
     spec: list of (name, 'float'|'int64', size); shuffle_buf <= 0 keeps file order;
-    seed None = OS-seeded (the reference's shuffle is unseeded)."""
+    seed None = OS-seeded (the reference's shuffle is unseeded); rename: {feature name: batch
+    key} for features delivered under another key than their name in the records."""
 
-    def __init__(self, files, spec, batch, repeat=1, shuffle_buf=0, seed=None, threads=10, depth=4):
-        self.spec = [(n, k, int(s)) for n, k, s in spec]
+    def __init__(self, files, spec, batch, repeat=1, shuffle_buf=0, seed=None, threads=10, depth=4, rename=None):
+        rename = rename or {}
+        self._keep = [n.encode() for n, _, _ in spec]       # the records' feature names
+        self.spec = [(rename.get(n, n), k, int(s)) for n, k, s in spec]
         self.batch = int(batch)
         L = lib()
         names = [f.encode() for f in files]
         farr = (C.c_char_p * max(1, len(names)))(*names)
-        self._keep = [n.encode() for n, _, _ in self.spec]
         feats = (_Feature * len(self.spec))(*[
             _Feature(self._keep[i], INT64 if k == "int64" else FLOAT, s) for i, (_, k, s) in enumerate(self.spec)])
         self.h = L.dlio_open(farr, len(names), feats, len(self.spec), self.batch, int(repeat), int(shuffle_buf),

@@ -502,6 +502,51 @@ int dl_wdl_head_fwd_bwd_bf16(int32_t B, int32_t Fw, int32_t H, const int64_t* wi
                              const float* label, float eps, float inv_batch, float* score, float* z_out,
                              float* dz, uint16_t* dh, int64_t* g_w, uint8_t* touched, float* slab,
                              int32_t slab_blocks, int32_t* err, void* stream);
+/* ------------------------------------------------------------------------
+ * Sample weights: tf.losses.log_loss(label, out, weights=w), TF 1.x's default reduction
+ * SUM_BY_NONZERO_WEIGHTS (the reference leaves weights at 1):
+ *   loss = sum_b w_b l_b / N_nz,  N_nz = #{b : w_b != 0}  (0 when N_nz == 0: div_no_nan),
+ *   dz_b = (dl_b/dp) (w_b inv_norm) p (1 - p),  inv_norm = N_nz ? 1 / N_nz : 0,
+ * with the effective weight w_b = weight_b * (1 + (pos_weight - 1) * y_b).
+ *
+ * dl_weight_norm: from weight [B] (NULL: all ones), label [B] and pos_weight (finite, > 0) writes
+ * w_eff [B] (two separately rounded f32 operations: f = 1 + (pos_weight - 1) y, w = weight f) and
+ * norm = {inv_norm, N_nz} (two floats; N_nz counted in integers in a fixed order, inv_norm =
+ * (float)(1.0 / (double)N_nz): all-ones weights give the f32 the unweighted step's 1 / B is).
+ * A weight that is negative, NaN or infinite sets DL_STATUS_BAD_WEIGHT in err[0] (the batch's
+ * validation word, beside DL_STATUS_BAD_ID: the step applies nothing) and gets w_eff = 0.  Runs
+ * after dl_validate_batch's reset of the word, before dl_step_begin.  One block; B <= 2^24.
+ *
+ * The *_weighted head entry points are their unweighted namesakes with (w_eff, norm) in place of
+ * inv_batch: scale = w_eff[b] * norm[0] stands where inv_batch stands, and the slab's loss column
+ * sums w_eff[b] * loss_b.  With all-ones weights they write the namesake's bits. */
+int dl_weight_norm(const float* weight, const float* label, int32_t B, float pos_weight, float* w_eff,
+                   float* norm, int32_t* err, void* stream);
+int dl_head_fwd_bwd_weighted(int32_t B, int32_t fm_cols, int32_t H, const float* fm_out, int32_t fm_ld,
+                             const float* h, int32_t ldh, const float* w, const float* label, float eps,
+                             const float* w_eff, const float* norm, float* score, float* z_out, float* dz,
+                             float* dh, float* slab, int32_t slab_blocks, void* stream);
+int dl_head_fwd_bwd_fmdrop_weighted(int32_t B, int32_t fm_cols, int32_t H, const float* fm_out, int32_t fm_ld,
+                                    const float* h, int32_t ldh, const float* w, const float* label, float eps,
+                                    const float* w_eff, const float* norm, float* score, float* z_out, float* dz,
+                                    float* dh, float* slab, int32_t slab_blocks, int32_t F, uint32_t keep_thr1,
+                                    float inv1, uint32_t keep_thr2, float inv2, uint64_t seed, const float* opt,
+                                    uint64_t* fm_keep, void* stream);
+int dl_wdl_head_fwd_bwd_weighted(int32_t B, int32_t Fw, int32_t H, const int64_t* wide, int32_t wide_ld,
+                                 const float* h, int32_t ldh, const float* w, const float* bias, int64_t w_rows,
+                                 const float* label, float eps, const float* w_eff, const float* norm, float* score,
+                                 float* z_out, float* dz, float* dh, int64_t* g_w, uint8_t* touched, float* slab,
+                                 int32_t slab_blocks, int32_t* err, void* stream);
+int dl_wdl_head_fwd_bwd_bf16_weighted(int32_t B, int32_t Fw, int32_t H, const int64_t* wide, int32_t wide_ld,
+                                      const float* h, int32_t ldh, const float* w, const float* bias, int64_t w_rows,
+                                      const float* label, float eps, const float* w_eff, const float* norm,
+                                      float* score, float* z_out, float* dz, uint16_t* dh, int64_t* g_w,
+                                      uint8_t* touched, float* slab, int32_t slab_blocks, int32_t* err, void* stream);
+/* dl_loss_accumulate (below) with the data term's scale read from the device normaliser:
+ * acc[0] += sum_r slab[r * pitch + col] / N_nz (N_nz = norm[1]; nothing added when it is 0). */
+int dl_loss_accumulate_weighted(const float* slab, int32_t rows, int32_t pitch, int32_t col, const float* norm,
+                                float* opt, float reg_coef, double* acc, int32_t* status_ring, void* stream);
+
 /* g[row0+j] += sum over `blocks` slab rows of slab[blk*width + col0 + j], j < n, as int64
  * fixed point (units 1/DL_WIDE_GRAD_SCALE, the wide gradient's form). */
 int dl_slab_fold_rows(const float* slab, int32_t blocks, int32_t width, int32_t col0, int32_t n,
@@ -549,6 +594,7 @@ int dl_slab_fold_rows(const float* slab, int32_t blocks, int32_t width, int32_t 
 #define DL_STATUS_INDEX 4    /* a batch-index entry out of range (index consumers report, never skip silently) */
 #define DL_STATUS_OVERFLOW 8 /* sharded step: a rank had more unique rows for an owner than a block holds */
 #define DL_STATUS_DESYNC 16  /* sharded step: the ranks' headers named different global steps */
+#define DL_STATUS_BAD_WEIGHT 32 /* a sample weight that is negative, NaN or infinite (dl_weight_norm) */
 int dl_adam_begin_step(float* opt, float decay_rate, float decay_steps, void* stream);
 /* The step's skip word := the batch's validation bits (batch_err[0], written by
  * dl_index_build / dl_validate_batch) | the sticky internal-fault bits; a bad batch
@@ -963,6 +1009,15 @@ int dl_gauc(const float* scores, int64_t s_stride, const float* labels, int64_t 
 int64_t dl_eval_stats_workspace_bytes(int64_t n);
 int dl_eval_stats(const float* scores, int64_t s_stride, const float* labels, int64_t l_stride, int64_t n, double eps,
                   void* ws, int64_t ws_bytes, double* out, void* stream);
+/* dl_eval_stats with per-sample weights w (f32 widened to double, finite and >= 0):
+ *   out[0] = sum w l, out[1] = sum w p, out[2] = sum w y, out[3] = sum w, out[4] = #{w != 0}
+ * (l, p, y as in dl_eval_stats).  A weight that is negative, NaN or infinite makes all of
+ * out[0..3] NaN.  Same two fixed-order double stages.
+ * Workspace: dl_eval_stats_weighted_workspace_bytes(n) (-1 for n <= 0 or n > 2^31-1), 8-B aligned. */
+int64_t dl_eval_stats_weighted_workspace_bytes(int64_t n);
+int dl_eval_stats_weighted(const float* scores, int64_t s_stride, const float* labels, int64_t l_stride,
+                           const float* weights, int64_t w_stride, int64_t n, double eps, void* ws, int64_t ws_bytes,
+                           double* out, void* stream);
 /* Streaming copy of `bytes` (a multiple of 16, both pointers 16-B aligned) from src to dst: the
  * measured HBM yardstick bench.py reports beside the 8 TB/s specification (roofline.peak_measured). */
 int dl_hbm_copy(const void* src, void* dst, int64_t bytes, void* stream);

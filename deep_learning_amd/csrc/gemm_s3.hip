@@ -18,11 +18,11 @@
 //       k chunk.  Block 256 x 208 (8 waves x 32 rows x 13 column fragments).
 //   TN  C[M][N] = sum_k X[k][M] Y[k][N]  weight gradients, split-K slabs over the batch:
 //       both operands batch-major f32, split into planes on their way into LDS, read back as
-//       MFMA fragments by CDNA4's transposing ds_read_b64_tr_b16.  Block 128 x 416
-//       (8 waves x 32 rows x 13 column fragments).
+//       MFMA fragments by CDNA4's transposing ds_read_b64_tr_b16.  Block 128 x 224
+//       (8 waves x 32 rows x 7 column fragments), two LDS buffers, the next step's staging
+//       interleaved with this step's MFMAs.
 #include "common.h"
 #include "philox.h"
-#include <cstdlib>
 #include <type_traits>
 
 namespace dl {
@@ -133,54 +133,6 @@ struct S3Params {
 // [row][c >> 4] = h[row][c] > 0) instead of the f32 activations — 1/32 of the mask bytes
 enum { S3_STORE = 0, S3_RELU = 1, S3_MASK = 2, S3_MASKBITS = 3 };
 
-#ifndef DL_S3_MWLATE
-#define DL_S3_MWLATE 1   // dX bitmask words loaded before the last k step (0: before the main loop)
-#endif
-#ifndef DL_S3_GDIAG
-#define DL_S3_GDIAG 0   // diagnostics build: the gathered A rows all read table row 0 (timing only)
-#endif
-#ifndef DL_S3_BPF
-#define DL_S3_BPF 0   // 1: NT pins the next fragment's weight reads ahead of this one's MFMAs
-#endif                // (sched_barrier; measured slower than leaving the order to the scheduler)
-
-#ifndef DL_S3_PF
-#define DL_S3_PF 1    // NT: weight fragments read this many fragments ahead of their MFMAs
-#endif
-#ifndef DL_S3_SGB
-#define DL_S3_SGB 0   // NT: pin the order (fragment f + PF's LDS reads, then fragment f's 12 MFMAs)
-#endif                // with sched_group_barrier, so the reads are not sunk next to their use
-
-#ifndef DL_S3_ASMB
-#define DL_S3_ASMB 0  // NT: the weight fragments' LDS reads as inline asm, DL_S3_PF fragments ahead,
-#endif                // each fragment's MFMAs behind a hand-counted lgkmcnt wait tied to its registers
-
-#ifndef DL_S3_ESPLIT
-#define DL_S3_ESPLIT 1   // NT: chunk c + 1's A planes split in the middle of chunk c's MFMAs
-                         // (fwd_l1 114.7 -> 110.9 us alone, profiles/r05f/s3_ab.txt)
-#endif
-#ifndef DL_S3_ESASM
-#define DL_S3_ESASM 1   // early-split step: weight fragment reads as asm, DL_S3_ES_PF fragments ahead
-#endif
-#ifndef DL_S3_ES_PF
-#define DL_S3_ES_PF 2
-#endif
-
-#ifndef DL_S3_TNSTAG
-#define DL_S3_TNSTAG 0   // TN2: waves 4-7 split + store the next step's tiles BEFORE their MFMAs
-#endif                   // (waves 0-3 after), so the two waves of a SIMD overlap VALU/LDS with MFMA
-
-#ifndef DL_S3_TN2
-#define DL_S3_TN2 1   // weight gradients: the double-buffered TN kernel (0: the single-buffer one)
-#endif
-
-#ifndef DL_S3_DIAG
-#define DL_S3_DIAG 0   // diagnostics builds: 1 = no epilogue stores, 2 = no MFMAs either;
-                       // 3 = no stores, no A loads (constant A); 4 = no stores, no B LDS reads;
-                       // 5 = no stores, no per-chunk barrier; 6 = no plane split (A in NT, both
-                       // operands in TN2: the f32 bits taken as planes); 7 = NT A pieces at k = 32c + 4kq
-                       // and + 16 (results wrong: timing only)
-#endif
-
 // ---------------------------------------------------------------------------- NT
 // B chunk images: per plane 208 rows x 32 k (64 B), 16-B piece kq of row j at slot
 // kq ^ ((j >> 2) & 2): conflict-free fragment reads for ds_read_b128's four lane groups
@@ -225,7 +177,7 @@ __device__ __forceinline__ void nt_rd3(uint32_t a, shortx8& h, shortx8& m, short
 // DIRECT: the transposed accumulator layout (mfma_s3_t) and the epilogue straight from registers
 // — one 16-B store of four consecutive columns per lane and fragment (a wave instruction writes
 // 16 rows x 64 B), ReLU / ReluGrad bitmask in registers — instead of the transpose through the
-// LDS ring; the bitmask words the dX epilogue needs are loaded before the main loop.  Needs
+// LDS ring; the bitmask words the dX epilogue needs are loaded before the last k step.  Needs
 // N % 4 == 0, ldc % 4 == 0 and an even ldbits (the host picks it then; otherwise the LDS form).
 // GATHER: the embedding-lookup fusion of the flushed-table forward (dl_gemm_s3_nt_gather): the
 // first 32 g_chunks columns of A are fetched row by row from the table through the ids (an 8-float
@@ -241,6 +193,7 @@ __device__ __forceinline__ void nt_rd3(uint32_t a, shortx8& h, shortx8& m, short
 // S3_MASKBITS reads that combined mask and scales what it lets through by inv (no RNG).
 template <int EPI, bool DIRECT = false, bool GATHER = false, bool STORE_A = false, bool DROP = false>
 __global__ __launch_bounds__(512) void gemm_s3_nt_kernel(S3Params p) {
+  static_assert(!(DIRECT && EPI == S3_MASK), "the f32-mask epilogue goes through LDS (s3_nt_direct)");
   extern __shared__ __attribute__((aligned(16))) unsigned short lds[];   // [3 bufs][3 planes][BN][32]
   constexpr int NW = 8, BM = kNtBM, DMAW = kNtDmaW;
   const unsigned short* __restrict__ Bp = reinterpret_cast<const unsigned short*>(p.B);
@@ -333,14 +286,10 @@ __global__ __launch_bounds__(512) void gemm_s3_nt_kernel(S3Params p) {
         return;
       }
     }
-    if (DL_S3_DIAG == 3) {
-      ra[0] = ra[1] = ra[2] = ra[3] = make_float4(1.f + c, 2.f, 3.f, 4.f);
-      return;
-    }
     // DL_S3_KPERM (common.h s3_kpos): a whole chunk's pieces at k = 32c + 4kq and + 16, so
     // each instruction reads one contiguous 64-B half line per row instead of four 16-B pieces
-    // of a whole line (DL_S3_DIAG 7: the same loads against natural-order planes, timing only)
-    const bool perm = (DL_S3_KPERM || DL_S3_DIAG == 7) && 32 * c + 32 <= p.K;
+    // of a whole line
+    const bool perm = DL_S3_KPERM && 32 * c + 32 <= p.K;
     const int k = perm ? 32 * c + 4 * kq : 32 * c + 8 * kq;
     const uint32_t d2 = perm ? 64u : 16u;
     const bool kin = k < p.K;
@@ -375,7 +324,6 @@ __global__ __launch_bounds__(512) void gemm_s3_nt_kernel(S3Params p) {
       }
     }
   };
-  if (!DL_S3_MWLATE) load_mw();
 
   float4 raA[4], raB[4];
   // prologue: B chunks 0 and 1 in flight, A chunks 0 and 1
@@ -423,8 +371,7 @@ __global__ __launch_bounds__(512) void gemm_s3_nt_kernel(S3Params p) {
           const int rr = i / p.g_fields, f = i - rr * p.g_fields;
           const long long id = idv[u] + p.id_off;
           const bool v = id >= 0 && id < p.n_rows && (id > 0 || !p.zero_row0);
-          // DL_S3_GDIAG (diagnostics build, wrong results): every valid reference reads row 0
-          gtab[f * kNtGfs + rr] = v ? (DL_S3_GDIAG ? 0u : (uint32_t)id * (uint32_t)(4 * p.g_ld)) : kNtGmasked;
+          gtab[f * kNtGfs + rr] = v ? (uint32_t)id * (uint32_t)(4 * p.g_ld) : kNtGmasked;
         }
       }
     }
@@ -459,7 +406,6 @@ __global__ __launch_bounds__(512) void gemm_s3_nt_kernel(S3Params p) {
   // chunk 0's B must have landed
   publish(-1);
 
-#if DL_S3_ESPLIT
   if constexpr (EPI != S3_MASK) {
     // Early split: chunk c + 1's A planes are split in the middle of chunk c's fragments (its
     // MFMAs issue beside the VALU work), so after each barrier the waves start on MFMAs instead of
@@ -493,39 +439,25 @@ __global__ __launch_bounds__(512) void gemm_s3_nt_kernel(S3Params p) {
     auto step_es = [&](int c, shortx8 (&P)[6], shortx8 (&Pn)[6], float4 (&R)[4], float4 (&F)[4]) {
       load_a(c + 2, F);
       asm volatile("" ::: "memory");   // the loads issue here, not sunk to the mid-step split
+      // the fragments' LDS byte address: fragment f's rows 16f + cl sit 1,024 B apart (the
+      // swizzle slot depends only on cl and kq), planes 13,312 B apart
       const uint32_t b_addr = lds_base + 2u * (uint32_t)((c % 3) * kNtBuf + cl * 32 + 8 * nt_slot(cl, kq));
-      const unsigned short* Bs = lds + (c % 3) * kNtBuf;
-      auto rd_b = [&](int f, shortx8& bh, shortx8& bm, shortx8& bl) {
-        const int j = 16 * f + cl;
-        const int o = j * 32 + 8 * nt_slot(j, kq);
-        bh = *reinterpret_cast<const shortx8*>(&Bs[o]);
-        bm = *reinterpret_cast<const shortx8*>(&Bs[kNtPlane + o]);
-        bl = *reinterpret_cast<const shortx8*>(&Bs[2 * kNtPlane + o]);
-      };
-      (void)b_addr;
-      (void)rd_b;
-      // DL_S3_ESASM: each fragment's three plane reads as asm issued ES_PF fragments ahead, and an
-      // lgkmcnt wait tied to its registers right before its MFMAs (hipcc, left alone, issued
-      // each pair of fragments' reads just ahead of their MFMAs: the LDS latency in the MFMA
-      // stream once a pair); same operands, same order of products
-      constexpr int EPF = DL_S3_ESASM ? DL_S3_ES_PF : 1, ENB = EPF + 1;
+      // Each fragment's three plane reads as asm issued EPF fragments ahead, and an lgkmcnt
+      // wait tied to its registers right before its MFMAs (hipcc, left alone, issued each pair
+      // of fragments' reads just ahead of their MFMAs: the LDS latency in the MFMA stream once
+      // a pair); same operands, same order of products
+      constexpr int EPF = 2, ENB = EPF + 1;
       shortx8 bb[ENB][3];
 #pragma unroll
-      for (int i = 0; i < EPF; ++i) {
-        if (DL_S3_ESASM) nt_rd3(b_addr + 1024u * i, bb[i][0], bb[i][1], bb[i][2]);
-        else rd_b(i, bb[i][0], bb[i][1], bb[i][2]);
-      }
+      for (int i = 0; i < EPF; ++i) nt_rd3(b_addr + 1024u * i, bb[i][0], bb[i][1], bb[i][2]);
 #pragma unroll
       for (int f = 0; f < kNtNF; ++f) {
-        if (f + EPF < kNtNF) {
-          if (DL_S3_ESASM) nt_rd3(b_addr + 1024u * (f + EPF), bb[(f + EPF) % ENB][0], bb[(f + EPF) % ENB][1], bb[(f + EPF) % ENB][2]);
-          else rd_b(f + EPF, bb[(f + EPF) % ENB][0], bb[(f + EPF) % ENB][1], bb[(f + EPF) % ENB][2]);
-        }
-        if (DL_S3_ESASM) {
+        if (f + EPF < kNtNF)
+          nt_rd3(b_addr + 1024u * (f + EPF), bb[(f + EPF) % ENB][0], bb[(f + EPF) % ENB][1], bb[(f + EPF) % ENB][2]);
+        {
           shortx8 &h = bb[f % ENB][0], &m = bb[f % ENB][1], &l = bb[f % ENB][2];
           const int younger = min(EPF, kNtNF - 1 - f);   // fragments whose reads follow f's
-          if (younger >= 3) DL_LDS_WAIT(9, h, m, l);
-          else if (younger == 2) DL_LDS_WAIT(6, h, m, l);
+          if (younger == 2) DL_LDS_WAIT(6, h, m, l);
           else if (younger == 1) DL_LDS_WAIT(3, h, m, l);
           else DL_LDS_WAIT(0, h, m, l);
         }
@@ -550,20 +482,15 @@ __global__ __launch_bounds__(512) void gemm_s3_nt_kernel(S3Params p) {
       step_es(c, pA, pB, raB, raA);
       step_es(c + 1, pB, pA, raA, raB);
     }
-    if (DL_S3_MWLATE) load_mw();   // under the peeled last step's MFMAs (odd KC), else before the epilogue
+    load_mw();   // under the peeled last step's MFMAs (odd KC), else before the epilogue
     if (c < KC) step_es(c, pA, pB, raB, raA);
-  } else
-#endif
-  {
+  } else {
+  // S3_MASK (the f32 ReluGrad mask): the plain step.  The host never pairs it with DIRECT, so
+  // there is no transposed-accumulator arm here and no bitmask words to load.
   auto step = [&](int c, float4 (&ra)[4]) {
     shortx8 ah[2], am[2], al[2];
-    if (DL_S3_DIAG == 6) {   // timing only: the f32 bits taken as planes, no split
-      ah[0] = __builtin_bit_cast(shortx8, ra[0]); am[0] = __builtin_bit_cast(shortx8, ra[1]); al[0] = ah[0];
-      ah[1] = __builtin_bit_cast(shortx8, ra[2]); am[1] = __builtin_bit_cast(shortx8, ra[3]); al[1] = ah[1];
-    } else {
-      split8(ra[0], ra[1], ah[0], am[0], al[0]);
-      split8(ra[2], ra[3], ah[1], am[1], al[1]);
-    }
+    split8(ra[0], ra[1], ah[0], am[0], al[0]);
+    split8(ra[2], ra[3], ah[1], am[1], al[1]);
     // hipcc's wait for chunk c's A counts only its own loads (4 a batch), so it must come
     // before the next batch is issued or it would also wait for part of that batch: the empty
     // statement pins the split (and its wait) ahead of the batch's DMA statements
@@ -575,66 +502,25 @@ __global__ __launch_bounds__(512) void gemm_s3_nt_kernel(S3Params p) {
     auto rd_b = [&](int f, shortx8& bh, shortx8& bm, shortx8& bl) {
       const int j = 16 * f + cl;
       const int o = j * 32 + 8 * nt_slot(j, kq);
-      if (DL_S3_DIAG == 4) {
-        bh = am[0]; bm = al[1]; bl = ah[1];
-      } else {
-        bh = *reinterpret_cast<const shortx8*>(&Bs[o]);
-        bm = *reinterpret_cast<const shortx8*>(&Bs[kNtPlane + o]);
-        bl = *reinterpret_cast<const shortx8*>(&Bs[2 * kNtPlane + o]);
-      }
+      bh = *reinterpret_cast<const shortx8*>(&Bs[o]);
+      bm = *reinterpret_cast<const shortx8*>(&Bs[kNtPlane + o]);
+      bl = *reinterpret_cast<const shortx8*>(&Bs[2 * kNtPlane + o]);
     };
     // every fragment, also those past N (clamped weight rows, products discarded by the
     // epilogue): no per-fragment branch, so the scheduler hoists fragment f + PF's reads over
     // fragment f's MFMAs instead of each fragment waiting out its own LDS latency
-    constexpr int PF = DL_S3_PF;
-    shortx8 bb[PF + 1][3];
-    // the fragments' LDS byte address: fragment f's rows 16f + cl sit 1,024 B apart (the
-    // swizzle slot depends only on cl and kq), planes 13,312 B apart
-    const uint32_t b_addr = lds_base + 2u * (uint32_t)((c % 3) * kNtBuf + cl * 32 + 8 * nt_slot(cl, kq));
+    constexpr int PF = 1, NB = PF + 1;
+    shortx8 bb[NB][3];
 #pragma unroll
-    for (int i = 0; i < PF; ++i) {
-      if (DL_S3_ASMB) nt_rd3(b_addr + 1024u * i, bb[i][0], bb[i][1], bb[i][2]);
-      else rd_b(i, bb[i][0], bb[i][1], bb[i][2]);
-    }
+    for (int i = 0; i < PF; ++i) rd_b(i, bb[i][0], bb[i][1], bb[i][2]);
 #pragma unroll
     for (int f = 0; f < kNtNF; ++f) {
-      {
-        constexpr int NB = PF + 1;
-        if (f + PF < kNtNF) {
-          if (DL_S3_ASMB) nt_rd3(b_addr + 1024u * (f + PF), bb[(f + PF) % NB][0], bb[(f + PF) % NB][1], bb[(f + PF) % NB][2]);
-          else rd_b(f + PF, bb[(f + PF) % NB][0], bb[(f + PF) % NB][1], bb[(f + PF) % NB][2]);
-        }
-        if (DL_S3_ASMB) {
-          shortx8 &h = bb[f % NB][0], &m = bb[f % NB][1], &l = bb[f % NB][2];
-          if (f + PF < kNtNF) {           // fragments f + 1 .. f + PF may stay in flight
-            if (PF == 1) DL_LDS_WAIT(3, h, m, l);
-            else if (PF == 2) DL_LDS_WAIT(6, h, m, l);
-            else DL_LDS_WAIT(9, h, m, l);
-          } else if (f + 1 < kNtNF) {     // the tail: only fragment f + 1's reads remain younger
-            DL_LDS_WAIT(3, h, m, l);
-          } else {
-            DL_LDS_WAIT(0, h, m, l);
-          }
-        }
-        const shortx8 bh = bb[f % NB][0], bm = bb[f % NB][1], bl = bb[f % NB][2];
-        if (DL_S3_BPF) __builtin_amdgcn_sched_barrier(0);   // keep them there
-        if (DL_S3_DIAG == 2) {
-          acc[0][f][0] += (float)(bh[0] ^ ah[0][1] ^ bm[2] ^ bl[3] ^ am[0][0] ^ al[0][2]);
-          acc[1][f][0] += (float)(bh[1] ^ ah[1][1] ^ bm[3] ^ bl[4] ^ am[1][0] ^ al[1][2]);
-        } else if (DIRECT) {
-          acc[0][f] = mfma_s3_t(ah[0], am[0], al[0], bh, bm, bl, acc[0][f]);
-          acc[1][f] = mfma_s3_t(ah[1], am[1], al[1], bh, bm, bl, acc[1][f]);
-        } else {
-          acc[0][f] = mfma_s3(ah[0], am[0], al[0], bh, bm, bl, acc[0][f]);
-          acc[1][f] = mfma_s3(ah[1], am[1], al[1], bh, bm, bl, acc[1][f]);
-        }
-        if (DL_S3_SGB) {
-          if (f + PF < kNtNF) __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);   // 3 DS reads
-          __builtin_amdgcn_sched_group_barrier(0x008, 12, 0);                     // then 12 MFMAs
-        }
-      }
+      if (f + PF < kNtNF) rd_b(f + PF, bb[(f + PF) % NB][0], bb[(f + PF) % NB][1], bb[(f + PF) % NB][2]);
+      const shortx8 bh = bb[f % NB][0], bm = bb[f % NB][1], bl = bb[f % NB][2];
+      acc[0][f] = mfma_s3(ah[0], am[0], al[0], bh, bm, bl, acc[0][f]);
+      acc[1][f] = mfma_s3(ah[1], am[1], al[1], bh, bm, bl, acc[1][f]);
     }
-    if (DL_S3_DIAG != 5) publish(c);
+    publish(c);
   };
   // pairs of unconditional steps (an odd last chunk after the loop): at the loop head the
   // latest batch is always raB's, so hipcc's own wait for raA leaves that batch in flight
@@ -643,19 +529,9 @@ __global__ __launch_bounds__(512) void gemm_s3_nt_kernel(S3Params p) {
     step(c, raA);
     step(c + 1, raB);
   }
-  if (DL_S3_MWLATE) load_mw();
   if (c < KC) step(c, raA);
   }
 
-  if (DL_S3_DIAG && DL_S3_DIAG != 6 && DL_S3_DIAG != 7) {   // keep the loop's results live without storing them
-    float tt = 0.f;
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-      for (int f = 0; f < kNtNF; ++f) tt += acc[a][f][0] + acc[a][f][3];
-    if (tt == 12345.f) p.C[0] = tt;
-    return;
-  }
   if constexpr (DIRECT) {
     // lane (kq, cl): acc[a][f][j] = C[r0 + 16a + cl][j0 + 16f + 4kq + j].  Stores go through a
     // buffer descriptor: a piece past M or N gets an offset past its range and is dropped.
@@ -845,19 +721,35 @@ __global__ __launch_bounds__(512) void gemm_s3_nt_kernel(S3Params p) {
 }
 
 // ---------------------------------------------------------------------------- TN
-// Block: 128 rows (m) x 416 columns (n) of a split-K slab, 8 waves: wave w owns rows
-// 32 (w & 3) .. +32 (2 fragments) x columns 208 (w >> 2) .. +208 (13 fragments).  Per
-// 32-deep batch step the f32 tiles X[k][m0..m0+128) and Y[k][0..416) are loaded into
-// registers one step ahead, split, and written to LDS as three plane images each
-// ([k][m], [k][n]; pitches 144 and 432 bf16 = 8 x odd words: conflict-free transposed
-// reads).  Lane group kq reads batch rows 4kq..4kq+3 and 16+4kq..16+4kq+3 for both operands
-// (the same k set, so the sum is unchanged).
-constexpr int kTnBM = 128, kTnBN = 416, kTnKS = 32, kTnPA = 144, kTnPB = 432;
-constexpr int kTnAE = kTnKS * kTnPA, kTnBE = kTnKS * kTnPB;          // elements per plane image
-constexpr int kTnQA = kTnKS * kTnBM / 4, kTnQB = kTnKS * kTnBN / 4;  // float4 pieces per step
-constexpr int kTnQ = (kTnQA + kTnQB + 511) / 512;
-constexpr size_t kTnLds = 3 * (kTnAE + kTnBE) * sizeof(unsigned short);
-static_assert(kTnQA == 2 * 512 && kTnQB == 6 * 512 + 256 && kTnQ == 9, "the TN piece mapping below");
+// The weight gradients, one split-K slab a block.  Block: 128 rows (m) x 224 columns (n), 8 waves:
+// wave w owns rows 32 (w >> 1) .. +32 (2 fragments) x columns 112 (w & 1) .. +112 (7 fragments);
+// N takes ceil(N / 224) column tiles (N = 400: 2), the column tiles of one (m, slab) adjacent
+// in the grid so they share X in L2.  Per 32-deep batch step the f32 tiles X[k][m0 .. m0 + 128)
+// and Y[k][n0 .. n0 + 224) are split and written to LDS as three plane images each ([k][m],
+// [k][n]; pitches 144 and 240 bf16 = 8 x odd words: conflict-free transposed reads).  Lane group
+// kq reads batch rows 4kq .. 4kq + 3 and 16 + 4kq .. 16 + 4kq + 3 for both operands (the same k
+// set, so the sum is unchanged).
+// Two LDS buffers (2 x 73.7 KB of the 160 KB): a step computes from buffer kt & 1 while the next
+// step's tiles go into the other, and one barrier per step publishes them.  The staging runs
+// under the MFMAs: the f32 tiles are loaded two steps ahead (two register sets), and step
+// kt + 1's six pieces per thread are split and stored between step kt's fragment groups (piece b
+// after fragment b's twelve MFMAs), so each wave's VALU split and LDS stores issue while its
+// MFMAs execute instead of in a phase of their own between barriers (staged in its own phase,
+// the MFMAs were busy about half the loop).
+// A thread's pieces (float4): u = 0, 1 -> X rows (tid >> 5) + 16u, columns 4 (tid & 31);
+// u = 2..5 -> Y piece tid + 512 (u - 2) = row piece / 56, column 4 (piece % 56) (u = 5: threads
+// < 256 only).  Loads go through buffer descriptors: an offset past the range reads zeros.
+// A wave whose row fragments lie past M (the last row tile: M = 400 leaves 1 of its 8 fragment
+// rows in range, 432 leaves 3) skips their MFMAs and fragment reads, and the waves of one
+// fragment row sit on different SIMDs (wm = wid >> 1), so such a block costs about its split
+// work plus the valid rows' MFMAs instead of a full tile's.
+constexpr int kT2BM = 128, kT2BN = 224, kT2KS = 32, kT2PA = 144, kT2PB = 240, kT2NF = 7;
+constexpr int kT2AE = kT2KS * kT2PA, kT2BE = kT2KS * kT2PB;           // bf16 elements per plane image
+constexpr int kT2Buf = 3 * (kT2AE + kT2BE);                           // one buffer: A planes, B planes
+constexpr size_t kT2Lds = 2 * kT2Buf * sizeof(unsigned short);       // 147,456 B
+constexpr int kT2QA = kT2KS * kT2BM / 4, kT2QB = kT2KS * kT2BN / 4;   // float4 pieces per step
+constexpr int kT2Q = (kT2QA + kT2QB + 511) / 512;
+static_assert(kT2QA == 2 * 512 && kT2QB == 3 * 512 + 256 && kT2Q == 6, "the piece mapping below");
 
 __device__ __forceinline__ uint2 s3_lds_tr16(const unsigned short* ptr_) {
   auto lp = (__attribute__((address_space(3))) unsigned short*)(const_cast<unsigned short*>(ptr_));
@@ -872,311 +764,6 @@ __device__ __forceinline__ shortx8 s3_tr_frag(const unsigned short* img, int pit
   return __builtin_bit_cast(shortx8, make_uint4(lo.x, lo.y, hi.x, hi.y));
 }
 
-__global__ __launch_bounds__(512) void gemm_s3_tn_kernel(S3Params p) {
-  extern __shared__ __attribute__((aligned(16))) unsigned short lds[];   // [3][KS][PA] then [3][KS][PB]
-  unsigned short* As = lds;
-  unsigned short* Bs = lds + 3 * kTnAE;
-  const float* __restrict__ X = p.A;
-  const float* __restrict__ Y = reinterpret_cast<const float*>(p.B);
-  const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int mtiles = (p.M + kTnBM - 1) / kTnBM;
-  const int t = s3_xcd_tile(blockIdx.x, gridDim.x);
-  const int m0 = (t % mtiles) * kTnBM, z = t / mtiles;
-  const int kbeg = z * p.k_per_split;
-  const int kend = min(p.K, kbeg + p.k_per_split);
-  const int nk = (kend - kbeg + kTnKS - 1) / kTnKS;
-  const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
-  // Pieces of a step: 1024 A pieces (32 rows x 32 float4 of X) are u = 0, 1; then 3328 B pieces
-  // (32 rows x 104 float4 of Y) are u = 2..8 (u = 8: threads < 256 only).  Each thread's pieces
-  // sit at fixed offsets: loads go unconditionally to clamped addresses and out-of-range
-  // pieces are zeroed afterwards (no exec-masked loads).
-  float4 rs[kTnQ];
-  const int qa_r0 = tid >> 5, qa_c = 4 * (tid & 31);                 // u = 0: row qa_r0, u = 1: row qa_r0 + 16
-  const bool qa_ok = m0 + qa_c < p.M;
-  const float* xa = X + min(m0 + qa_c, p.M - 4);
-  int qb_r[7], qb_c[7];
-  bool qb_ok[7];
-#pragma unroll
-  for (int u = 0; u < 7; ++u) {
-    const int qq = tid + 512 * u;
-    qb_r[u] = qq / 104;
-    qb_c[u] = 4 * (qq % 104);
-    qb_ok[u] = qb_c[u] < p.N && (u < 6 || tid < 256);
-  }
-  auto load = [&](int k0) {
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      const int gk = k0 + qa_r0 + 16 * u;
-      const float4 v = *reinterpret_cast<const float4*>(xa + (long long)min(gk, kend - 1) * p.lda);
-      rs[u] = (qa_ok && gk < kend) ? v : z4;
-    }
-#pragma unroll
-    for (int u = 0; u < 7; ++u) {
-      const int gk = k0 + min(qb_r[u], kTnKS - 1);
-      const float4 v = *reinterpret_cast<const float4*>(Y + (long long)min(gk, kend - 1) * p.ldb +
-                                                          min(qb_c[u], p.N - 4));
-      rs[2 + u] = (qb_ok[u] && gk < kend) ? v : z4;
-    }
-  };
-  auto store = [&]() {
-#pragma unroll
-    for (int u = 0; u < kTnQ; ++u) {
-      uint32_t h0, m0_, l0, h1, m1_, l1;
-      split2(rs[u].x, rs[u].y, h0, m0_, l0);
-      split2(rs[u].z, rs[u].w, h1, m1_, l1);
-      if (u < 2) {
-        const int o = (qa_r0 + 16 * u) * kTnPA + qa_c;
-        *reinterpret_cast<uint2*>(&As[o]) = make_uint2(h0, h1);
-        *reinterpret_cast<uint2*>(&As[kTnAE + o]) = make_uint2(m0_, m1_);
-        *reinterpret_cast<uint2*>(&As[2 * kTnAE + o]) = make_uint2(l0, l1);
-      } else if (u < 8 || tid < 256) {
-        const int o = qb_r[u - 2] * kTnPB + qb_c[u - 2];
-        *reinterpret_cast<uint2*>(&Bs[o]) = make_uint2(h0, h1);
-        *reinterpret_cast<uint2*>(&Bs[kTnBE + o]) = make_uint2(m0_, m1_);
-        *reinterpret_cast<uint2*>(&Bs[2 * kTnBE + o]) = make_uint2(l0, l1);
-      }
-    }
-  };
-  floatx4 acc[2][13];
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < 13; ++b) acc[a][b] = floatx4{0.f, 0.f, 0.f, 0.f};
-  const int wm = wid & 3, wn = wid >> 2;
-  const int cl = lane & 15, kq = lane >> 4, rq = cl >> 2, cp = cl & 3;
-  const int ra = 4 * kq + rq, rb = 16 + 4 * kq + rq;
-  // fragments whose rows / columns lie past M / N are skipped (wave-uniform)
-  const int ma_live = min(2, max(0, (p.M - (m0 + 32 * wm) + 15) / 16));
-  const int nb_live = min(13, max(0, (p.N - 208 * wn + 15) / 16));
-  if (nk > 0) {
-    load(kbeg);
-    store();
-    __syncthreads();
-  }
-  for (int kt = 0; kt < nk; ++kt) {
-    if (kt + 1 < nk) load(kbeg + (kt + 1) * kTnKS);
-    shortx8 ah[2], am[2], al[2];
-#pragma unroll
-    for (int a = 0; a < 2; ++a) {
-      const int col = 32 * wm + 16 * a + 4 * cp;
-      ah[a] = s3_tr_frag(As, kTnPA, ra, rb, col);
-      am[a] = s3_tr_frag(As + kTnAE, kTnPA, ra, rb, col);
-      al[a] = s3_tr_frag(As + 2 * kTnAE, kTnPA, ra, rb, col);
-    }
-#pragma unroll
-    for (int b = 0; b < 13; ++b) {
-      if (b < nb_live) {
-        const int col = 208 * wn + 16 * b + 4 * cp;
-        const shortx8 bh = s3_tr_frag(Bs, kTnPB, ra, rb, col);
-        const shortx8 bm = s3_tr_frag(Bs + kTnBE, kTnPB, ra, rb, col);
-        const shortx8 bl = s3_tr_frag(Bs + 2 * kTnBE, kTnPB, ra, rb, col);
-#pragma unroll
-        for (int a = 0; a < 2; ++a)
-          if (a < ma_live) acc[a][b] = mfma_s3(ah[a], am[a], al[a], bh, bm, bl, acc[a][b]);
-      }
-    }
-    __syncthreads();
-    if (kt + 1 < nk) {
-      store();
-      __syncthreads();
-    }
-  }
-  float* __restrict__ C = p.C + (long long)z * p.c_split_stride;
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < 13; ++b) {
-      const int col = 208 * wn + 16 * b + cl;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int row = m0 + 32 * wm + 16 * a + 4 * kq + j;
-        if (row < p.M && col < p.N) C[(long long)row * p.ldc + col] = acc[a][b][j];
-      }
-    }
-}
-
-// ---------------------------------------------------------------------------- TN, double-buffered
-// The weight gradients again, with two LDS buffers so a step's MFMAs never wait for the next
-// step's staging: per 32-deep batch step a wave computes from buffer kt & 1 while the next
-// step's tiles (loaded into registers at the step's start) are split and written into the
-// other buffer, and one barrier per step publishes them.  Two 73.7 KB buffers fit the 160 KB
-// LDS at a 128 x 224 block (8 waves: rows 32 (w & 3) .. +32 = 2 fragments, columns 112 (w >> 2)
-// .. +112 = 7 fragments); N takes ceil(N / 224) column tiles (N = 400: 2).  Pitches 144 and
-// 240 bf16 (8 x odd words: conflict-free transposed reads, as above).  Out-of-range pieces
-// are loaded through buffer descriptors with an offset past the range: zeros, no fixup.
-constexpr int kT2BM = 128, kT2BN = 224, kT2KS = 32, kT2PA = 144, kT2PB = 240, kT2NF = 7;
-constexpr int kT2AE = kT2KS * kT2PA, kT2BE = kT2KS * kT2PB;           // bf16 elements per plane image
-constexpr int kT2Buf = 3 * (kT2AE + kT2BE);                           // one buffer: A planes, B planes
-constexpr size_t kT2Lds = 2 * kT2Buf * sizeof(unsigned short);       // 147,456 B
-constexpr int kT2QA = kT2KS * kT2BM / 4, kT2QB = kT2KS * kT2BN / 4;   // float4 pieces per step
-constexpr int kT2Q = (kT2QA + kT2QB + 511) / 512;
-static_assert(kT2QA == 2 * 512 && kT2QB == 3 * 512 + 256 && kT2Q == 6, "the piece mapping below");
-
-__global__ __launch_bounds__(512) void gemm_s3_tn2_kernel(S3Params p) {
-  extern __shared__ __attribute__((aligned(16))) unsigned short lds[];   // [2][3 A planes | 3 B planes]
-  const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int mtiles = (p.M + kT2BM - 1) / kT2BM, ntiles = (p.N + kT2BN - 1) / kT2BN;
-  const int t = s3_xcd_tile(blockIdx.x, gridDim.x);   // the column tiles of one (m, slab) adjacent: X shared in L2
-  const int n0 = (t % ntiles) * kT2BN, m0 = ((t / ntiles) % mtiles) * kT2BM, z = t / (ntiles * mtiles);
-  const int kbeg = z * p.k_per_split;
-  const int kend = min(p.K, kbeg + p.k_per_split);
-  const int nk = (kend - kbeg + kT2KS - 1) / kT2KS;
-  const auto xr = __builtin_amdgcn_make_buffer_rsrc((void*)p.A, (short)0, p.K * p.lda * 4, 0x00020000);
-  const auto yr = __builtin_amdgcn_make_buffer_rsrc((void*)p.B, (short)0, p.K * p.ldb * 4, 0x00020000);
-  // this thread's pieces: u = 0, 1 -> X rows (tid >> 5) + 16u, columns 4 (tid & 31); u = 2..5 ->
-  // Y piece tid + 512 (u - 2) = row / 56, column 4 (piece % 56) (u = 5: threads < 256 only)
-  int pr[kT2Q], pc[kT2Q];
-  bool pok[kT2Q];
-#pragma unroll
-  for (int u = 0; u < kT2Q; ++u) {
-    if (u < 2) {
-      pr[u] = (tid >> 5) + 16 * u;
-      pc[u] = 4 * (tid & 31);
-      pok[u] = m0 + pc[u] < p.M;
-    } else {
-      const int qb = tid + 512 * (u - 2);
-      pr[u] = qb / (kT2BN / 4);
-      pc[u] = 4 * (qb % (kT2BN / 4));
-      pok[u] = n0 + pc[u] < p.N && (u < 5 || tid < 256);
-    }
-  }
-  float4 rs[kT2Q];
-  auto load = [&](int k0) {
-#pragma unroll
-    for (int u = 0; u < kT2Q; ++u) {
-      const int gk = k0 + pr[u];
-      const bool ok = pok[u] & (gk < kend);   // no short circuit: a select, not a branch
-      if (u < 2) {
-        const uint32_t o = 4u * (uint32_t)(gk * p.lda + m0 + pc[u]);
-        rs[u] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(xr, (int)(ok ? o : 0x80000000u), 0, 0));
-      } else {
-        const uint32_t o = 4u * (uint32_t)(gk * p.ldb + n0 + pc[u]);
-        rs[u] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(yr, (int)(ok ? o : 0x80000000u), 0, 0));
-      }
-    }
-  };
-  auto store = [&](int buf) {
-    unsigned short* As = lds + buf * kT2Buf;
-    unsigned short* Bs = As + 3 * kT2AE;
-#pragma unroll
-    for (int u = 0; u < kT2Q; ++u) {
-      if (u == 5 && tid >= 256) continue;
-      uint32_t h0, m0_, l0, h1, m1_, l1;
-      if (DL_S3_DIAG == 6) {   // timing only: no split
-        h0 = __float_as_uint(rs[u].x); m0_ = __float_as_uint(rs[u].y); l0 = h0;
-        h1 = __float_as_uint(rs[u].z); m1_ = __float_as_uint(rs[u].w); l1 = h1;
-      } else {
-        split2(rs[u].x, rs[u].y, h0, m0_, l0);
-        split2(rs[u].z, rs[u].w, h1, m1_, l1);
-      }
-      unsigned short* img = u < 2 ? As : Bs;
-      const int pe = u < 2 ? kT2AE : kT2BE;
-      const int o = pr[u] * (u < 2 ? kT2PA : kT2PB) + pc[u];
-      *reinterpret_cast<uint2*>(&img[o]) = make_uint2(h0, h1);
-      *reinterpret_cast<uint2*>(&img[pe + o]) = make_uint2(m0_, m1_);
-      *reinterpret_cast<uint2*>(&img[2 * pe + o]) = make_uint2(l0, l1);
-    }
-  };
-  floatx4 acc[2][kT2NF];
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < kT2NF; ++b) acc[a][b] = floatx4{0.f, 0.f, 0.f, 0.f};
-  const int wm = wid & 3, wn = wid >> 2;
-  const int cl = lane & 15, kq = lane >> 4, rq = cl >> 2, cp = cl & 3;
-  const int ra = 4 * kq + rq, rb = 16 + 4 * kq + rq;
-  auto compute = [&](int buf) {   // every fragment (zeros past M / N): no branches between them
-    const unsigned short* As = lds + buf * kT2Buf;
-    const unsigned short* Bs = As + 3 * kT2AE;
-    shortx8 ah[2], am[2], al[2];
-#pragma unroll
-    for (int a = 0; a < 2; ++a) {
-      const int col = 32 * wm + 16 * a + 4 * cp;
-      ah[a] = s3_tr_frag(As, kT2PA, ra, rb, col);
-      am[a] = s3_tr_frag(As + kT2AE, kT2PA, ra, rb, col);
-      al[a] = s3_tr_frag(As + 2 * kT2AE, kT2PA, ra, rb, col);
-    }
-#pragma unroll
-    for (int b = 0; b < kT2NF; ++b) {
-      const int col = 112 * wn + 16 * b + 4 * cp;
-      const shortx8 bh = s3_tr_frag(Bs, kT2PB, ra, rb, col);
-      const shortx8 bm = s3_tr_frag(Bs + kT2BE, kT2PB, ra, rb, col);
-      const shortx8 bl = s3_tr_frag(Bs + 2 * kT2BE, kT2PB, ra, rb, col);
-#pragma unroll
-      for (int a = 0; a < 2; ++a) acc[a][b] = mfma_s3(ah[a], am[a], al[a], bh, bm, bl, acc[a][b]);
-    }
-  };
-  if (DL_S3_TNSTAG) {
-    // Staggered roles (MI355X_MICROARCH.md, two waves per SIMD: waves w and w + 4 share one):
-    // waves 0-3 run [MFMAs of step kt][split + store of step kt + 1], waves 4-7 the reverse, so
-    // on every SIMD one wave's VALU/LDS work runs beside the other's MFMAs.  The registers
-    // hold step kt + 1's tiles from the load issued after the previous store; the barrier
-    // waits only for this wave's LDS writes (a __syncthreads would also drain the loads in
-    // flight, vmcnt(0)).
-    if (nk > 0) {
-      load(kbeg);
-      store(0);
-      if (nk > 1) load(kbeg + kT2KS);
-    }
-    __builtin_amdgcn_s_waitcnt(0xc07f);   // lgkmcnt(0)
-    __builtin_amdgcn_s_barrier();
-    const bool late = wid >= 4;
-    for (int kt = 0; kt < nk; ++kt) {
-      const bool more = kt + 1 < nk;
-      if (!late) compute(kt & 1);
-      if (more) {
-        store((kt + 1) & 1);            // the other buffer: its last readers passed the previous barrier
-        if (kt + 2 < nk) load(kbeg + (kt + 2) * kT2KS);
-      }
-      if (late) compute(kt & 1);
-      __builtin_amdgcn_s_waitcnt(0xc07f);
-      __builtin_amdgcn_s_barrier();
-    }
-  } else {
-    if (nk > 0) {
-      load(kbeg);
-      store(0);
-    }
-    __syncthreads();
-    for (int kt = 0; kt < nk; ++kt) {
-      const bool more = kt + 1 < nk;
-      if (more) load(kbeg + (kt + 1) * kT2KS);
-      compute(kt & 1);
-      if (more) store((kt + 1) & 1);   // the other buffer: its last readers passed the previous barrier
-      __syncthreads();
-    }
-  }
-  float* __restrict__ C = p.C + (long long)z * p.c_split_stride;
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < kT2NF; ++b) {
-      const int col = n0 + 112 * wn + 16 * b + cl;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int row = m0 + 32 * wm + 16 * a + 4 * kq + j;
-        if (row < p.M && col < p.N) C[(long long)row * p.ldc + col] = acc[a][b][j];
-      }
-    }
-}
-
-// ---------------------------------------------------------------------------- TN, interleaved
-// The double-buffered TN kernel with its staging moved under the MFMAs: the f32 tiles are
-// loaded two steps ahead (two register sets), and step kt + 1's six pieces per thread are split
-// and written to the other LDS buffer between step kt's fragment groups (piece b after fragment
-// b's twelve MFMAs), so each wave's VALU split and LDS stores issue while its MFMAs execute
-// instead of in a phase of their own between barriers (tn2: MFMA busy about half the loop).
-// Same tiles, images, fragment reads and k order as tn2: the same sums bit for bit.
-#ifndef DL_S3_TN3
-#define DL_S3_TN3 1   // weight gradients: the interleaved kernel (0: tn2)
-#endif
-
-
-// SKIP: a wave whose row fragments lie past M (the last row tile: M = 400 leaves 1 of its 8
-// fragment rows in range, 432 leaves 3) skips their MFMAs and fragment reads, and the waves of
-// one fragment row sit on different SIMDs (wm = wid >> 1), so such a block costs about its
-// split work plus the valid rows' MFMAs instead of a full tile's.
-template <bool SKIP>
 __global__ __launch_bounds__(512) void gemm_s3_tn3_kernel(S3Params p) {
   extern __shared__ __attribute__((aligned(16))) unsigned short lds[];   // [2][3 A planes | 3 B planes]
   const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1225,13 +812,8 @@ __global__ __launch_bounds__(512) void gemm_s3_tn3_kernel(S3Params p) {
     unsigned short* As = lds + buf * kT2Buf;
     unsigned short* Bs = As + 3 * kT2AE;
     uint32_t h0, m0_, l0, h1, m1_, l1;
-    if (DL_S3_DIAG == 6) {   // timing only: no split
-      h0 = __float_as_uint(r.x); m0_ = __float_as_uint(r.y); l0 = h0;
-      h1 = __float_as_uint(r.z); m1_ = __float_as_uint(r.w); l1 = h1;
-    } else {
-      split2(r.x, r.y, h0, m0_, l0);
-      split2(r.z, r.w, h1, m1_, l1);
-    }
+    split2(r.x, r.y, h0, m0_, l0);
+    split2(r.z, r.w, h1, m1_, l1);
     unsigned short* img = u < 2 ? As : Bs;
     const int pe = u < 2 ? kT2AE : kT2BE;
     const int o = pr[u] * (u < 2 ? kT2PA : kT2PB) + pc[u];
@@ -1244,7 +826,7 @@ __global__ __launch_bounds__(512) void gemm_s3_tn3_kernel(S3Params p) {
   for (int a = 0; a < 2; ++a)
 #pragma unroll
     for (int b = 0; b < kT2NF; ++b) acc[a][b] = floatx4{0.f, 0.f, 0.f, 0.f};
-  const int wm = SKIP ? wid >> 1 : wid & 3, wn = SKIP ? wid & 1 : wid >> 2;
+  const int wm = wid >> 1, wn = wid & 1;
   const int cl = lane & 15, kq = lane >> 4, rq = cl >> 2, cp = cl & 3;
   const int ra = 4 * kq + rq, rb = 16 + 4 * kq + rq;
   // some row of this wave's fragments inside M (wave-uniform)
@@ -1304,7 +886,7 @@ __global__ __launch_bounds__(512) void gemm_s3_tn3_kernel(S3Params p) {
   // (a bare s_barrier after lgkmcnt(0): __syncthreads' fence would also wait for the loads of
   // two steps ahead)
   int kt = 0;
-  if (!SKIP || live) {
+  if (live) {
     for (; kt + 1 < nk; kt += 2) {
       load(kbeg + (kt + 2) * kT2KS, rA);
       step(kt, 0, rB);
@@ -1367,24 +949,6 @@ using namespace dl;
 
 extern "C" int dl_s3_kperm(void) { return DL_S3_KPERM; }
 
-// DL_S3_DIRECT=0 in the environment: the NT epilogue through LDS (A/B measurements)
-static bool s3_direct_enabled() {
-  static const bool on = [] {
-    const char* e = getenv("DL_S3_DIRECT");
-    return !(e && e[0] == '0');
-  }();
-  return on;
-}
-
-// DL_S3_TNSKIP=0: every wave of a TN block runs all its MFMAs (A/B measurements)
-static bool s3_tnskip_enabled() {
-  static const bool on = [] {
-    const char* e = getenv("DL_S3_TNSKIP");
-    return !(e && e[0] == '0');
-  }();
-  return on;
-}
-
 extern "C" int dl_split3(const float* src, int32_t rows, int32_t cols, int32_t lds, int32_t transpose,
                          uint16_t* dst, int32_t ldd, int64_t plane_stride, void* stream) {
   DL_CHECK_ARG(src && dst, "NULL pointer");
@@ -1421,9 +985,55 @@ static int s3_nt_check(int32_t M, int32_t N, int32_t K, const float* A, int32_t 
 }
 
 static bool s3_nt_direct(int32_t M, int32_t N, int32_t ldc, int32_t epi, const uint16_t* bits, int32_t ldbits) {
-  return s3_direct_enabled() && N % 4 == 0 && ldc % 4 == 0 && (!bits || ldbits % 2 == 0) &&
+  return N % 4 == 0 && ldc % 4 == 0 && (!bits || ldbits % 2 == 0) &&
          epi != S3_MASK && (long long)M * ldc * 4 < (1LL << 31) &&
          (epi != S3_MASKBITS || ldbits >= 2 * ((((int)ceil_div(N, kNtBN) - 1) * kNtBN >> 5) + 7));
+}
+
+// The fields every NT form shares; a form adds its own block (dropout, gather) before the launch.
+static S3Params s3_nt_params(int32_t M, int32_t N, int32_t K, const float* A, int32_t lda, const uint16_t* Bp,
+                             int32_t ldb, int64_t b_plane, float* C, int32_t ldc, const float* mask, int32_t ldm,
+                             uint16_t* bits, int32_t ldbits) {
+  S3Params p{};
+  p.A = A; p.B = Bp; p.C = C; p.mask = mask;
+  p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldb = ldb; p.ldc = ldc; p.ldm = ldm; p.b_plane = b_plane;
+  p.bits = bits; p.ldbits = ldbits;
+  return p;
+}
+
+// One form at one epilogue: the register epilogue where the shape allows it, else the LDS one
+// (always, for the f32 mask), over one block a tile; a gather's offset table follows the ring.
+template <int EPI, bool GATHER = false, bool STORE_A = false, bool DROP = false>
+static void s3_nt_run(const S3Params& p, void* stream) {
+  const bool direct = s3_nt_direct(p.M, p.N, p.ldc, EPI, p.bits, p.ldbits);
+  const dim3 grid((unsigned)(ceil_div(p.M, kNtBM) * ceil_div(p.N, kNtBN)));
+  const size_t lds = kNtLds + (GATHER ? (size_t)p.g_fields * kNtGfs * 4 : 0);
+  if constexpr (EPI != S3_MASK) {
+    if (direct) {
+      hipLaunchKernelGGL((gemm_s3_nt_kernel<EPI, true, GATHER, STORE_A, DROP>), grid, dim3(512), lds, as_stream(stream), p);
+      return;
+    }
+  }
+  hipLaunchKernelGGL((gemm_s3_nt_kernel<EPI, false, GATHER, STORE_A, DROP>), grid, dim3(512), lds, as_stream(stream), p);
+}
+
+// The instantiated NT kernels, all of them: plain x {store, relu, mask, bitmask}, dropout x {relu,
+// bitmask}, gather (p.G) x {store, relu} x {the training form (p.a_store), not}; the entry points
+// have checked that epi is one of its form's.
+static void s3_nt_launch(const S3Params& p, int epi, bool drop, void* stream) {
+  if (drop) {
+    if (epi == S3_RELU) s3_nt_run<S3_RELU, false, false, true>(p, stream);
+    else s3_nt_run<S3_MASKBITS, false, false, true>(p, stream);
+  } else if (p.G && p.a_store) {
+    if (epi == S3_STORE) s3_nt_run<S3_STORE, true, true>(p, stream);
+    else s3_nt_run<S3_RELU, true, true>(p, stream);
+  } else if (p.G) {
+    if (epi == S3_STORE) s3_nt_run<S3_STORE, true>(p, stream);
+    else s3_nt_run<S3_RELU, true>(p, stream);
+  } else if (epi == S3_STORE) s3_nt_run<S3_STORE>(p, stream);
+  else if (epi == S3_RELU) s3_nt_run<S3_RELU>(p, stream);
+  else if (epi == S3_MASK) s3_nt_run<S3_MASK>(p, stream);
+  else s3_nt_run<S3_MASKBITS>(p, stream);
 }
 
 extern "C" int dl_gemm_s3_nt_bits(int32_t M, int32_t N, int32_t K, const float* A, int32_t lda, const uint16_t* Bp,
@@ -1431,21 +1041,8 @@ extern "C" int dl_gemm_s3_nt_bits(int32_t M, int32_t N, int32_t K, const float* 
                                   int32_t ldm, uint16_t* bits, int32_t ldbits, void* stream) {
   if (int rc = s3_nt_check(M, N, K, A, lda, Bp, ldb, b_plane, C, ldc, epi, mask, bits, ldbits)) return rc;
   if (M == 0 || N == 0) return 0;
-  S3Params p{};
-  p.A = A; p.B = Bp; p.C = C; p.mask = mask;
-  p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldb = ldb; p.ldc = ldc; p.ldm = ldm; p.b_plane = b_plane;
-  p.bits = bits; p.ldbits = ldbits;
-  hipStream_t s = as_stream(stream);
-  const bool direct = s3_nt_direct(M, N, ldc, epi, bits, ldbits);
-  const int tiles = (int)(ceil_div(M, kNtBM) * ceil_div(N, kNtBN));
-  if (direct) {
-    if (epi == S3_STORE) hipLaunchKernelGGL((gemm_s3_nt_kernel<S3_STORE, true>), dim3(tiles), dim3(512), kNtLds, s, p);
-    else if (epi == S3_RELU) hipLaunchKernelGGL((gemm_s3_nt_kernel<S3_RELU, true>), dim3(tiles), dim3(512), kNtLds, s, p);
-    else hipLaunchKernelGGL((gemm_s3_nt_kernel<S3_MASKBITS, true>), dim3(tiles), dim3(512), kNtLds, s, p);
-  } else if (epi == S3_STORE) hipLaunchKernelGGL(gemm_s3_nt_kernel<S3_STORE>, dim3(tiles), dim3(512), kNtLds, s, p);
-  else if (epi == S3_RELU) hipLaunchKernelGGL(gemm_s3_nt_kernel<S3_RELU>, dim3(tiles), dim3(512), kNtLds, s, p);
-  else if (epi == S3_MASK) hipLaunchKernelGGL(gemm_s3_nt_kernel<S3_MASK>, dim3(tiles), dim3(512), kNtLds, s, p);
-  else hipLaunchKernelGGL(gemm_s3_nt_kernel<S3_MASKBITS>, dim3(tiles), dim3(512), kNtLds, s, p);
+  const S3Params p = s3_nt_params(M, N, K, A, lda, Bp, ldb, b_plane, C, ldc, mask, ldm, bits, ldbits);
+  s3_nt_launch(p, epi, false, stream);
   DL_RETURN_LAUNCH("dl_gemm_s3_nt");
 }
 
@@ -1458,22 +1055,10 @@ extern "C" int dl_gemm_s3_nt_drop(int32_t M, int32_t N, int32_t K, const float* 
   DL_CHECK_ARG(opt, "opt is NULL");
   DL_CHECK_ARG(layer >= 0 && inv >= 1.f && inv < 3.4e38f, "bad dropout layer %d / factor %g", layer, (double)inv);
   if (M == 0 || N == 0) return 0;
-  S3Params p{};
-  p.A = A; p.B = Bp; p.C = C; p.mask = mask;
-  p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldb = ldb; p.ldc = ldc; p.ldm = ldm; p.b_plane = b_plane;
-  p.bits = bits; p.ldbits = ldbits;
+  S3Params p = s3_nt_params(M, N, K, A, lda, Bp, ldb, b_plane, C, ldc, mask, ldm, bits, ldbits);
   p.drop_thr = keep_thr; p.drop_inv = inv; p.drop_k0 = (uint32_t)seed; p.drop_k1 = (uint32_t)(seed >> 32);
   p.drop_layer = (uint32_t)layer; p.opt = opt;
-  hipStream_t s = as_stream(stream);
-  const bool direct = s3_nt_direct(M, N, ldc, epi, bits, ldbits);
-  const int tiles = (int)(ceil_div(M, kNtBM) * ceil_div(N, kNtBN));
-#define DL_S3D(E_, D_) hipLaunchKernelGGL((gemm_s3_nt_kernel<E_, D_, false, false, true>), dim3(tiles), dim3(512), kNtLds, s, p)
-  if (direct) {
-    if (epi == S3_RELU) DL_S3D(S3_RELU, true);
-    else DL_S3D(S3_MASKBITS, true);
-  } else if (epi == S3_RELU) DL_S3D(S3_RELU, false);
-  else DL_S3D(S3_MASKBITS, false);
-#undef DL_S3D
+  s3_nt_launch(p, epi, true, stream);
   DL_RETURN_LAUNCH("dl_gemm_s3_nt_drop");
 }
 
@@ -1496,30 +1081,14 @@ static int s3_nt_gather_launch(int32_t M, int32_t N, int32_t K, const float* A, 
   DL_CHECK_ARG((unsigned long long)n_rows * table_ld * 4 < kNtGmasked,
                "gather: the table spans %lld bytes (past the 32-bit buffer range)", (long long)n_rows * table_ld * 4);
   if (M == 0 || N == 0) return 0;
-  S3Params p{};
-  p.A = A; p.B = Bp; p.C = C;
-  p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldb = ldb; p.ldc = ldc; p.b_plane = b_plane;
-  p.bits = bits; p.ldbits = ldbits;
+  S3Params p = s3_nt_params(M, N, K, A, lda, Bp, ldb, b_plane, C, ldc, nullptr, 0, bits, ldbits);
   p.G = table; p.ids = ids; p.ids32 = ids32; p.a_store = a_store;
   p.id_off = id_offset; p.n_rows = n_rows; p.ids_ld = ids_ld; p.g_ld = table_ld;
   p.g_fields = fields; p.g_esh = __builtin_ctz(emb_dim); p.g_chunks = fields * emb_dim / 32;
   p.zero_row0 = zero_row0 ? 1 : 0;
   p.g_bytes = (unsigned)(n_rows * table_ld * 4);
   p.gofs = gofs;
-  hipStream_t s = as_stream(stream);
-  const bool direct = s3_nt_direct(M, N, ldc, epi, bits, ldbits);
-  const int tiles = (int)(ceil_div(M, kNtBM) * ceil_div(N, kNtBN));
-  const size_t lds = kNtLds + (size_t)fields * kNtGfs * 4;
-#define DL_S3G(E_, D_, ST_) hipLaunchKernelGGL((gemm_s3_nt_kernel<E_, D_, true, ST_>), dim3(tiles), dim3(512), lds, s, p)
-  if (a_store) {   // the training form: int32 rows, x0 written
-    if (direct) { if (epi == S3_STORE) DL_S3G(S3_STORE, true, true); else DL_S3G(S3_RELU, true, true); }
-    else if (epi == S3_STORE) DL_S3G(S3_STORE, false, true);
-    else DL_S3G(S3_RELU, false, true);
-  } else if (direct) {
-    if (epi == S3_STORE) DL_S3G(S3_STORE, true, false); else DL_S3G(S3_RELU, true, false);
-  } else if (epi == S3_STORE) DL_S3G(S3_STORE, false, false);
-  else DL_S3G(S3_RELU, false, false);
-#undef DL_S3G
+  s3_nt_launch(p, epi, false, stream);
   DL_RETURN_LAUNCH("dl_gemm_s3_nt_gather");
 }
 
@@ -1567,9 +1136,8 @@ extern "C" int dl_gemm_s3_tn(int32_t M, int32_t N, int32_t K, const float* X, in
                              void* stream) {
   DL_CHECK_ARG(M >= 0 && N >= 0 && K >= 0, "negative dims");
   DL_CHECK_ARG(X && Y && C, "NULL operand");
-  DL_CHECK_ARG(DL_S3_TN2 || N <= kTnBN, "N %d > %d", N, kTnBN);
   DL_CHECK_ARG(M % 4 == 0 && N % 4 == 0 && (M == 0 || M >= 4) && (N == 0 || N >= 4), "M, N must be multiples of 4");
-  DL_CHECK_ARG(!DL_S3_TN2 || ((long long)(K + 1) * lda * 4 < (1LL << 31) && (long long)(K + 1) * ldb * 4 < (1LL << 31)),
+  DL_CHECK_ARG((long long)(K + 1) * lda * 4 < (1LL << 31) && (long long)(K + 1) * ldb * 4 < (1LL << 31),
                "X / Y past the 31-bit buffer range");
   DL_CHECK_ARG(lda % 4 == 0 && ldb % 4 == 0 && lda >= (M + 3) / 4 * 4 && ldb >= (N + 3) / 4 * 4 && ldc >= N,
                "bad leading dims");
@@ -1585,18 +1153,7 @@ extern "C" int dl_gemm_s3_tn(int32_t M, int32_t N, int32_t K, const float* X, in
   p.k_per_split = kps;
   p.c_split_stride = c_split_stride;
   splits = (int)ceil_div(K > 0 ? K : 1, kps);
-  if (DL_S3_TN2 && DL_S3_TN3) {
-    const int tiles = (int)(ceil_div(M, kT2BM) * ceil_div(N, kT2BN));
-    if (s3_tnskip_enabled())
-      hipLaunchKernelGGL(gemm_s3_tn3_kernel<true>, dim3((unsigned)(tiles * splits)), dim3(512), kT2Lds, as_stream(stream), p);
-    else
-      hipLaunchKernelGGL(gemm_s3_tn3_kernel<false>, dim3((unsigned)(tiles * splits)), dim3(512), kT2Lds, as_stream(stream), p);
-  } else if (DL_S3_TN2) {
-    const int tiles = (int)(ceil_div(M, kT2BM) * ceil_div(N, kT2BN));
-    hipLaunchKernelGGL(gemm_s3_tn2_kernel, dim3((unsigned)(tiles * splits)), dim3(512), kT2Lds, as_stream(stream), p);
-  } else {
-    const int mtiles = (int)ceil_div(M, kTnBM);
-    hipLaunchKernelGGL(gemm_s3_tn_kernel, dim3((unsigned)(mtiles * splits)), dim3(512), kTnLds, as_stream(stream), p);
-  }
+  const int tiles = (int)(ceil_div(M, kT2BM) * ceil_div(N, kT2BN));
+  hipLaunchKernelGGL(gemm_s3_tn3_kernel, dim3((unsigned)(tiles * splits)), dim3(512), kT2Lds, as_stream(stream), p);
   DL_RETURN_LAUNCH("dl_gemm_s3_tn");
 }

@@ -370,9 +370,51 @@ def test_gemm_s3_nt_gather_argument_checks(hip_lib):
              432, 16 * 432, ptr(C_), 16, 1, None, 0, _s())
 
 
+def test_gemm_s3_nt_argument_checks(hip_lib):
+    """Every s3 entry point refuses a bad argument with its own message before it launches
+    anything (the NT forms share one launcher: none may lose a check), and one valid call of
+    each returns 0."""
+    M, N, K = 16, 16, 8
+    A = torch.zeros(M, 16, device="cuda")
+    Bp = _planes(torch.zeros(N, K, device="cuda"), False)
+    C_ = torch.zeros(2, M, N, device="cuda")
+    bits = torch.zeros(M, 2, dtype=torch.int16, device="cuda")
+    opt = torch.zeros(_lib.OPT_LEN, device="cuda")
+
+    def nt(K=K, lda=16, epi=0, mask=None):
+        return ("dl_gemm_s3_nt", M, N, K, ptr(A), lda, ptr(Bp), 8, N * 8, ptr(C_), N, epi, ptr(mask), N, _s())
+
+    def nt_bits(epi=1, b=bits, ldbits=2):
+        return ("dl_gemm_s3_nt_bits", M, N, K, ptr(A), 16, ptr(Bp), 8, N * 8, ptr(C_), N, epi, None, 0, ptr(b), ldbits,
+                _s())
+
+    def nt_drop(epi=1, o=opt, inv=2.0):
+        b = (ptr(bits), 2) if epi else (None, 0)
+        return ("dl_gemm_s3_nt_drop", M, N, K, ptr(A), 16, ptr(Bp), 8, N * 8, ptr(C_), N, epi, None, 0, *b,
+                1 << 31, inv, 2019, 1, ptr(o), _s())
+
+    def tn(M=M, splits=1, stride=M * N):
+        return ("dl_gemm_s3_tn", M, N, K, ptr(A), 16, ptr(A), 16, ptr(C_), N, splits, stride, _s())
+
+    for args, msg in [(nt(K=12), "multiple of 8"), (nt(lda=6), "leading dims"), (nt(epi=2), "needs mask"),
+                      (nt(epi=3), "bad epilogue"), (nt_bits(epi=3, b=None), "needs the bitmask"),
+                      (nt_bits(ldbits=0), "ldbits"), (nt_bits(epi=0), "a bitmask goes with"),
+                      (nt_drop(epi=0), "dropout goes with"), (nt_drop(o=None), "opt is NULL"),
+                      (nt_drop(inv=0.5), "bad dropout"), (tn(M=6), "multiples of 4"),
+                      (tn(splits=2, stride=0), "slab stride")]:
+        with pytest.raises(_lib.DLError, match=msg):
+            call(*args)
+    for args in (nt(), nt_bits(), nt_drop(), tn()):
+        assert call(*args) == 0
+    torch.cuda.synchronize()
+
+
+# (132, 452, 96, 2): three 224-wide column tiles, the last 4 wide; (4, 4, 40, 1): one partly
+# filled tile, K below one slab
 @pytest.mark.parametrize("M,N,K,splits", [(432, 400, 65536, 64), (416, 400, 8192, 8), (428, 396, 5000, 3),
                                             (64, 16, 100, 1), (16, 416, 4096, 16), (400, 400, 8192, 8),
-                                            (404, 400, 2048, 2), (144, 400, 1024, 1)])
+                                            (404, 400, 2048, 2), (144, 400, 1024, 1), (132, 452, 96, 2),
+                                            (4, 4, 40, 1)])
 def test_gemm_s3_tn_split_slabs(hip_lib, M, N, K, splits):
     """Weight gradients X^T . dY as split-K slabs (K chunks rounded to 64): slab sums against
     fp64, slabs past the used count untouched."""

@@ -91,7 +91,6 @@ SIGNATURES = {
     "dl_embed_fwd_slots": (I32, [LP, P, P, P, P, P, P, P, P, P]),
     "dl_embed_fwd_gtab": (I32, [LP, P, I32, P, P, P, P, P, P, P, P, P]),
     "dl_embed_fwd_gtab_ok": (I32, [LP]),
-    "dl_embed_fwd_rec": (I32, [LP, P, I32, I32, P, P, P, P, P, P, I32, P, I32, P, P, P, P, P]),
     "dl_embed_fwd_rec_flat": (I32, [LP, P, I32, I32, P, P, P, P, P, P, P, P, P, P, P]),
     "dl_shard_gather": (I32, [P, P, P, I64, I32, P, P, P]),
     "dl_shard_scatter_add": (I32, [P, P, P, I64, I32, P, P, P, P]),
@@ -165,9 +164,6 @@ SIGNATURES = {
     "dl_adam_hist_record": (I32, [P, P, I32, P]),
     "dl_rec_stash_floats": (I32, [I32]),
     "dl_rec_gather": (I32, [LP, P, I32, I32, I32, P, P, I64, I32, P, I32, P, I32, P, P, P, P]),
-    "dl_rec_gather_scatter": (I32, [LP, P, I32, I32, I32, P, P, I64, P, P, P, I32, P, I32, P, P, P, P, P, P, P, P, P]),
-    "dl_pool_fwd_staged": (I32, [LP, P, P, P, P, P, I32, I32, P, P, P, P, P]),
-    "dl_embed_fwd_staged": (I32, [LP, P, P, P, I32, P, P, P, P, P, P]),
     "dl_rec_bwd_adam": (I32, [LP, P, I32, I32, I32, P, P, P, P, P, P, P, I32, I64, P, P, P, P, P, P, P, I32, P,
                               P, P, I64, P]),
     "dl_rec_bwd_adam_fmdrop": (I32, [LP, P, I32, I32, I32, P, P, P, P, P, P, P, I32, I64, P, P, P, P, P, P, P, I32, P,

@@ -33,19 +33,13 @@ struct EmbArgs {
   float* fm_out;
   float* fm_sum;
   int32_t* err;
-  // record mode (single GPU, lazy Adam): the cate rows are read straight from the row
-  // records and caught up to step opt[7] - lag in registers; `table` / `first_order`
-  // then hold only the C replicated FM cont-field rows (compact, caught up by dl_rec_gather)
+  // record mode (single GPU, lazy Adam, a flushed table): the cate rows are read straight from
+  // the row records, which must stand at step opt[7] - lag; `table` / `first_order` then hold
+  // only the C replicated FM cont-field rows (compact, from dl_rec_gather)
   const float* rec;
   RecCfg rc;
-  const float* hist;
   const float* opt;
   int lag;
-  // staged mode (with inv; the lazy single-GPU forward after dl_rec_gather_scatter): the FM
-  // reference (b, f) reads table row inv_base + b*S + f (the FM staging rows), its first-order
-  // output and the deep references' x0 columns are already written — only references whose
-  // row has no key (inv < 0: the zero row) are written here, as zeros
-  int staged;
   // (dl_embed_fwd_gtab) the deep references' row byte offsets for the fused first tower layer,
   // common.h kGtab* layout; the deep rows themselves are then not read here
   uint32_t* gtab;
@@ -78,12 +72,13 @@ constexpr int kMaxSlots = 128;     // FM slots + deep slots per sample
 #ifndef DL_POOL_DIAG
 #define DL_POOL_DIAG 0   // diagnostics builds (wrong results; the compacted pooling): 1 = every row read from row 0
 #endif                   // (cache-resident), 2 = no pooled / count / first-order output stores
-// REC: 0 dense table; 1 row records caught up in registers (lazy training); 2 row records
-// already caught up (a flushed table: predict after dl_rec_flush) — only each record's first
-// 128-B line is read (p and the first-order triple + stamp), a stale row faults (DL_STATUS_LAG).
+// REC: 0 dense table (or, with inv, the batch's compact rows); 2 row records already caught up
+// (a flushed table: predict after dl_rec_flush) — only each record's first 128-B line is read
+// (p and the first-order triple + stamp), a stale row faults (DL_STATUS_LAG); 3 the slot plane
+// of dl_rec_flush (each row and its first-order weight in one 2E-float slot).
 template <int E, int NPS, int REC = 0>
 // (two samples in flight a wave, DL_FWD_SPW below: 4 waves a SIMD, up to 128 VGPRs)
-__global__ __launch_bounds__(256, (REC == 1 || NPS > 5) ? 1
+__global__ __launch_bounds__(256, NPS > 5 ? 1
                                   : (NPS == 5 || (DL_FWD_SPW > 1 && (REC == 0 || REC == 3) && NPS <= 3)) ? 4
                                   : DL_FWD_MIN_WAVES)
 void embed_fwd_kernel(EmbArgs a) {
@@ -96,7 +91,7 @@ void embed_fwd_kernel(EmbArgs a) {
   // zeroed by select, never by a branch around the load.
   constexpr int LPR = E / 4;
   constexpr int RPI = 64 / LPR;
-  constexpr bool RECS = REC == 1 || REC == 2;          // the record modes
+  constexpr bool RECS = REC == 2;                      // the record mode
   constexpr int TP = REC == 3 ? 2 * LPR : LPR;         // float4s between table rows (slot plane: 2E floats)
   constexpr int W1S = REC == 3 ? 2 * E : 1;            // floats between first-order weights
   __shared__ int rows_s[kTileSamples][kMaxSlots];
@@ -114,17 +109,9 @@ void embed_fwd_kernel(EmbArgs a) {
   const int ntiles = (L.batch + kTileSamples - 1) / kTileSamples;
   RecCfg rc = a.rc;
   int target = 0;
-  extern __shared__ float hist_s[];   // record mode: the alpha ring, so the catch-up loop's
-                                      // per-step reads are LDS hits, not L2 round trips
   if (REC == 2) {
     target = (int)a.opt[7] - a.lag;
     rc.status = opt_status(a.opt);
-  }
-  if (REC == 1) {
-    rec_load_hyper(rc, a.opt);
-    target = (int)a.opt[7] - a.lag;
-    for (int k = threadIdx.x; k <= rc.hist_mask; k += blockDim.x) hist_s[k] = a.hist[k];
-    __syncthreads();
   }
 
   for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
@@ -141,10 +128,10 @@ void embed_fwd_kernel(EmbArgs a) {
           const int j = k / S, f = k % S;
           const int64_t rb = (int64_t)(b0 + j) * ns;
           const int di = a.inv[rb + (L.use_fm ? S : 0) + f];
-          rows_s[j][Fs + f] = di < 0 ? -1 : (a.staged ? -2 : a.inv_base + di);   // -2: written by the gather
+          rows_s[j][Fs + f] = di < 0 ? -1 : a.inv_base + di;
           if (L.use_fm) {
             const int fi = a.inv[rb + f];
-            rows_s[j][Cf + f] = fi < 0 ? -1 : a.inv_base + (a.staged ? (b0 + j) * S + f : fi);
+            rows_s[j][Cf + f] = fi < 0 ? -1 : a.inv_base + fi;
           }
         }
       } else {
@@ -203,7 +190,6 @@ void embed_fwd_kernel(EmbArgs a) {
       int rw[SPW][NPS];
       float w1[SPW], val[SPW];
       int frow[SPW];
-      bool w1_done[SPW];
 #pragma unroll
       for (int u = 0; u < SPW; ++u) {
         const int j = min(jw + 4 * u, nb - 1);   // past the tile: repeats its last sample, not written
@@ -217,7 +203,7 @@ void embed_fwd_kernel(EmbArgs a) {
         if (!RECS) {
 #pragma unroll
           for (int p = 0; p < NPS; ++p) v[u][p] = tab4[(int64_t)(rw[u][p] < 0 ? 0 : rw[u][p]) * TP + q];
-        } else if (REC == 2) {
+        } else {
           float4 t4[NPS];
 #pragma unroll
           for (int p = 0; p < NPS; ++p) {
@@ -238,48 +224,15 @@ void embed_fwd_kernel(EmbArgs a) {
               if (sl < Fs && rc.has_first && q == 0) a.fm_out[(int64_t)b * L.fm_ld + sl] = rw[u][p] < 0 ? 0.f : t4[p].x * 1.f;
             }
           }
-        } else {
-          // slots >= Cf: the whole record (p, m, v, first-order triple + stamp) is loaded for
-          // every pass before any is consumed, then caught up exactly as dl_rec_gather does
-          // (same catch_up4 on the same float4): the values are bit-identical to the
-          // gathered rows the indexed forward reads.
-          float4 m4[NPS], v4[NPS], t4[NPS];
-#pragma unroll
-          for (int p = 0; p < NPS; ++p) {
-            const int sl = p * RPI + r;
-            if (sl < Cf) {
-              v[u][p] = tab4[(rw[u][p] < 0 ? 0 : rw[u][p]) * LPR + q];
-            } else {
-              const float* rr = a.rec + (int64_t)(rw[u][p] < 0 ? 0 : rw[u][p]) * rc.ld;
-              v[u][p] = *reinterpret_cast<const float4*>(rr + 4 * q);
-              m4[p] = *reinterpret_cast<const float4*>(rr + E + 4 + 4 * q);
-              v4[p] = *reinterpret_cast<const float4*>(rr + 2 * E + 4 + 4 * q);
-              t4[p] = *reinterpret_cast<const float4*>(rr + E);
-            }
-          }
-#pragma unroll
-          for (int p = 0; p < NPS; ++p) {
-            const int sl = p * RPI + r;
-            if (sl >= Cf && sl < nslot) {
-              const bool fmf = sl < Fs && rc.has_first && q == 0;   // FM slot: its first-order weight too
-              float w = t4[p].x, wm = t4[p].y, wv = t4[p].z;
-              const int stamp = __float_as_int(t4[p].w);
-              if (stamp < target) catch_up4(v[u][p], m4[p], v4[p], w, wm, wv, fmf, stamp, target, RingG{hist_s, rc.hist_mask}, rc);
-              if (fmf) a.fm_out[(int64_t)b * L.fm_ld + sl] = rw[u][p] < 0 ? 0.f : w * 1.f;
-            }
-          }
         }
         // first-order terms (one lane per FM field; record mode: the cont fields only)
         w1[u] = 0.f;
         val[u] = 0.f;
         frow[u] = -1;
-        // staged: the FM cate fields' first-order outputs were written by the gather (their rows
-        // index the staging rows, not first_order) — only the zero rows' are written here
-        w1_done[u] = a.staged && lane >= Cf && lane < Fs && rows_s[j][lane] >= 0;
         if (lane < (RECS ? Cf : Fs)) {
           frow[u] = rows_s[j][lane];
           val[u] = lane < Cf ? vals_s[j][lane] : 1.f;
-          w1[u] = DL_POOL_DIAG_NO_W1 ? 1.f : a.first_order[(int64_t)((frow[u] < 0 || w1_done[u]) ? 0 : frow[u]) * W1S];
+          w1[u] = DL_POOL_DIAG_NO_W1 ? 1.f : a.first_order[(int64_t)(frow[u] < 0 ? 0 : frow[u]) * W1S];
         }
       }
 #pragma unroll
@@ -305,7 +258,7 @@ void embed_fwd_kernel(EmbArgs a) {
             s.x += ev.x; s.y += ev.y; s.z += ev.z; s.w += ev.w;
             ss.x = fmaf(ev.x, ev.x, ss.x); ss.y = fmaf(ev.y, ev.y, ss.y);
             ss.z = fmaf(ev.z, ev.z, ss.z); ss.w = fmaf(ev.w, ev.w, ss.w);
-          } else if (sl < nslot && rw[u][p] != -2) {
+          } else if (sl < nslot) {
             const int col = L.x0_cat_col + (sl - Fs) * E + 4 * q;
             if (L.x0_bf16)
               *reinterpret_cast<uint2*>(xbb + col) = make_uint2(f2bf(t4.x) | ((unsigned)f2bf(t4.y) << 16),
@@ -315,10 +268,9 @@ void embed_fwd_kernel(EmbArgs a) {
           }
         }
       }
-      if (lane < (RECS ? Cf : Fs) && !w1_done[u]) a.fm_out[(int64_t)b * L.fm_ld + lane] = frow[u] < 0 ? 0.f : w1[u] * val[u];
+      if (lane < (RECS ? Cf : Fs)) a.fm_out[(int64_t)b * L.fm_ld + lane] = frow[u] < 0 ? 0.f : w1[u] * val[u];
       for (int f = 64 + lane; f < (RECS ? 0 : Fs); f += 64) {   // > 64 FM fields (rare; record mode: <= 64)
         const int fr = rows_s[j][f];
-        if (a.staged && f >= Cf && fr >= 0) continue;
         const float vv = f < Cf ? vals_s[j][f] : 1.f;
         a.fm_out[(int64_t)b * L.fm_ld + f] = fr < 0 ? 0.f : a.first_order[(int64_t)fr * W1S] * vv;
       }
@@ -656,10 +608,6 @@ struct PoolArgs {
   int32_t* err;
   const float* vals;       // weighted mode: value of multi position l of sample b = vals[b*vals_ld + l]
   int vals_ld;
-  // staged mode (IDX; after dl_rec_gather_scatter with multi-hot staging): the row of multi
-  // position l of sample b is table row b * multi_width + l (written there by the gather),
-  // a position without a row (inv < 0: padding) none
-  int staged;
 };
 
 // One wave per sample.  A slot's positions are resolved 64 at a time, one per lane (ids or
@@ -697,7 +645,7 @@ __global__ __launch_bounds__(256) void pool_fwd_kernel(PoolArgs a) {
         if (lane < nl) {
           if (IDX) {
             const int ri = invb[c0 + lane];
-            src = ri < 0 ? -1 : a.staged ? (long long)b * L.multi_width + c0 + lane : (long long)a.inv_base + ri;
+            src = ri < 0 ? -1 : (long long)a.inv_base + ri;
           } else {
             const int64_t row = checked_row(ids[c0 + lane], 0, L.n_rows, a.err);
             src = row_ok(row, L.zero_row0) ? row : -1;
@@ -760,7 +708,7 @@ __global__ __launch_bounds__(256) void pool_fwd_kernel(PoolArgs a) {
 // the rows the sample references — padding costs no iteration and no predicated-off lanes —
 // and every slot's rows are in flight at once instead of slot after slot.  Per-slot sums stay in
 // registers (a lane's rows in queue order, then the xor tree over the 16 row groups): the
-// order depends only on the positions, so the dense, indexed and staged modes pool identically.
+// order depends only on the positions, so the dense and indexed modes pool identically.
 // deepfm_multi_cate.py:73-78: cnt = count_nonzero(reduce_sum(V[ids], axis=2)) per slot,
 // out = div_no_nan(reduce_sum(V[ids], axis=1), cnt); the first-order weights likewise.
 constexpr int kPoolMaxSlots = 8;
@@ -854,7 +802,7 @@ __global__ __launch_bounds__(256) void pool_fwd_compact_kernel(PoolArgs a) {
         if (m < M) {
           if (IDX) {
             const int ri = invb[pos];
-            src = ri < 0 ? -1 : a.staged ? b * L.multi_width + pos : a.inv_base + ri;
+            src = ri < 0 ? -1 : a.inv_base + ri;
           } else {
             const int64_t row = checked_row(ids[pos], 0, L.n_rows, a.err);
             src = row_ok(row, L.zero_row0) ? (int)row : -1;
@@ -1096,41 +1044,6 @@ extern "C" int dl_embed_fwd_indexed(const dl_emb_layout* L, const float* rows, c
   return launch_embed_fwd<0>(L, a, stream);
 }
 
-extern "C" int dl_embed_fwd_staged(const dl_emb_layout* L, const float* fmst, const float* rows_first,
-                                   const int32_t* inv, int32_t n_rep, const float* cont, const float* vector,
-                                   float* x0, float* fm_out, float* fm_sum, void* stream) {
-  if (int rc = check_layout(L)) return rc;
-  DL_CHECK_ARG(inv && x0, "NULL inv/x0");
-  DL_CHECK_ARG(!L->use_fm || (fmst && rows_first && fm_out && fm_sum), "FM inputs / outputs required");
-  DL_CHECK_ARG(!L->use_fm || !L->fm_cont || L->cont_rows_compact, "the FM cont-field rows come compact");
-  if (L->batch == 0) return 0;
-  EmbArgs a{*L, inv, n_rep, fmst ? fmst : x0, rows_first, nullptr, cont, vector, x0, fm_out, fm_sum, nullptr};
-  a.staged = 1;
-  return launch_embed_fwd<0>(L, a, stream);
-}
-
-extern "C" int dl_embed_fwd_rec(const dl_emb_layout* L, const float* rec, int32_t rec_ld, int32_t rec_flags,
-                                const float* rows_rep, const float* rows_rep1, const int64_t* cate,
-                                const float* cont, const float* vector, const float* hist, int32_t hist_len,
-                                const float* opt, int32_t lag, float* x0, float* fm_out, float* fm_sum,
-                                int32_t* err, void* stream) {
-  const int32_t has_first = rec_flags & DL_REC_FIRST;
-  if (int rc = check_layout(L)) return rc;
-  DL_CHECK_ARG(rec && cate && x0 && hist && opt, "NULL argument");
-  DL_CHECK_ARG(hist_len >= 2 && hist_len <= 8192 && (hist_len & (hist_len - 1)) == 0,
-               "hist_len must be a power of two in [2, 8192] (the ring is staged in LDS)");
-  DL_CHECK_ARG(rec_ld % 4 == 0 && rec_ld >= 3 * L->emb_dim + 4, "rec_ld %d too small", rec_ld);
-  DL_CHECK_ARG(L->multi_width == 0 && L->fm_extra == 0, "record forward: single-valued fields only");
-  const int Cf = (L->use_fm && L->fm_cont) ? L->cont_fields : 0;
-  DL_CHECK_ARG(Cf == 0 || (L->cont_rows_compact && rows_rep && (!has_first || rows_rep1)),
-               "the FM cont-field rows come compact in rows_rep / rows_rep1");
-  DL_CHECK_ARG(!L->use_fm || (fm_out && fm_sum && Cf + L->cate_fields <= 64), "FM outputs required (<= 64 fields)");
-  if (L->batch == 0) return 0;
-  EmbArgs a{*L, nullptr, 0, rows_rep, rows_rep1, cate, cont, vector, x0, fm_out, fm_sum, err,
-            rec, make_rec_cfg(L->emb_dim, rec_ld, rec_flags, hist_len), hist, opt, lag};
-  return launch_embed_fwd<1>(L, a, stream);
-}
-
 extern "C" int dl_embed_fwd_rec_flat(const dl_emb_layout* L, const float* rec, int32_t rec_ld, int32_t rec_flags,
                                      const float* rows_rep, const float* rows_rep1, const int64_t* cate,
                                      const float* cont, const float* vector, const float* opt, float* x0,
@@ -1146,7 +1059,7 @@ extern "C" int dl_embed_fwd_rec_flat(const dl_emb_layout* L, const float* rec, i
   DL_CHECK_ARG(!L->use_fm || (fm_out && fm_sum && Cf + L->cate_fields <= 64), "FM outputs required (<= 64 fields)");
   if (L->batch == 0) return 0;
   EmbArgs a{*L, nullptr, 0, rows_rep, rows_rep1, cate, cont, vector, x0, fm_out, fm_sum, err,
-            rec, make_rec_cfg(L->emb_dim, rec_ld, rec_flags, 2), nullptr, opt, 0};
+            rec, make_rec_cfg(L->emb_dim, rec_ld, rec_flags, 2), opt, 0};
   return launch_embed_fwd<2>(L, a, stream);
 }
 
@@ -1155,15 +1068,13 @@ static int launch_embed_fwd(const dl_emb_layout* L, const EmbArgs& a, void* stre
   DL_CHECK_ARG((L->use_fm ? (L->fm_cont ? L->cont_fields : 0) + 2 * L->cate_fields : L->cate_fields) <= kMaxSlots,
                "too many fields per sample for the gather kernel (max %d slots)", kMaxSlots);
   const int tiles = (L->batch + kTileSamples - 1) / kTileSamples;
-  const int gmax = REC == 1 ? 1024 : 8192;   // record mode: each block stages the alpha ring once
-  const dim3 grid(tiles < gmax ? tiles : gmax), block(256);
+  const dim3 grid(tiles < 8192 ? tiles : 8192), block(256);
   const int nslot = (L->use_fm ? (L->fm_cont ? L->cont_fields : 0) + L->cate_fields : 0) +
                     (L->x0_cat_col >= 0 ? L->cate_fields : 0);
   const int rpi = 64 / (L->emb_dim / 4);
   const int nps = nslot > 0 ? (nslot + rpi - 1) / rpi : 1;
-  const size_t lds = REC == 1 ? (size_t)(a.rc.hist_mask + 1) * sizeof(float) : 0;
   hipStream_t st = as_stream(stream);
-#define DL_FWD(E_, N_) hipLaunchKernelGGL((embed_fwd_kernel<E_, N_, REC>), grid, block, lds, st, a)
+#define DL_FWD(E_, N_) hipLaunchKernelGGL((embed_fwd_kernel<E_, N_, REC>), grid, block, 0, st, a)
   switch (L->emb_dim) {
     case 16:
       switch (nps) {
@@ -1279,25 +1190,6 @@ extern "C" int dl_pool_fwd_indexed(const dl_emb_layout* L, const float* rows, co
   else DL_DISPATCH_E(L->emb_dim, hipLaunchKernelGGL((pool_fwd_kernel<kE, true>), dim3(emb_grid(L->batch)),
                                                dim3(256), 0, as_stream(stream), a));
   DL_RETURN_LAUNCH("dl_pool_fwd_indexed");
-}
-
-extern "C" int dl_pool_fwd_staged(const dl_emb_layout* L, const float* mst, const float* mst1, const int32_t* inv,
-                                  const int32_t* slot_start, const int32_t* slot_end, int32_t n_slots, int32_t fm_col,
-                                  float* x0, float* fm_out, float* cnt_emb, float* cnt_first, void* stream) {
-  if (int rc = check_layout(L)) return rc;
-  DL_CHECK_ARG(mst && inv && x0 && cnt_emb && slot_start && slot_end && n_slots >= 0, "NULL argument");
-  DL_CHECK_ARG(L->multi_width > 0, "staged pooling needs the multi-hot refs in the index (multi_width)");
-  DL_CHECK_ARG(!mst1 || (fm_out && cnt_first), "first-order pooling needs fm_out/cnt_first");
-  if (L->batch == 0 || n_slots == 0) return 0;
-  PoolArgs a{*L, inv, 0, mst, mst1, nullptr, 0, slot_start, slot_end, n_slots, fm_col,
-             x0, fm_out, cnt_emb, cnt_first, nullptr, nullptr, 0};
-  a.staged = 1;
-  if (DL_POOL_COMPACT && n_slots <= kPoolMaxSlots)
-    DL_DISPATCH_E(L->emb_dim, hipLaunchKernelGGL((pool_fwd_compact_kernel<kE, true, false>), dim3(emb_grid(L->batch)),
-                                                 dim3(256), 0, as_stream(stream), a))
-  else DL_DISPATCH_E(L->emb_dim, hipLaunchKernelGGL((pool_fwd_kernel<kE, true>), dim3(emb_grid(L->batch)),
-                                               dim3(256), 0, as_stream(stream), a));
-  DL_RETURN_LAUNCH("dl_pool_fwd_staged");
 }
 
 static int pool_bwd_impl(const dl_emb_layout* L, const int64_t* ids, int32_t ids_col,

@@ -264,8 +264,7 @@ def _v_to_root(v):
 
 class CTREngine:
     def __init__(self, spec, max_batch, device="cuda", seed=2019, init="device", bwd="atomic",
-                 table_rows=None, adam="dense", hist_len=4096, rec_stash=True, fwd_rec=False, gemm="s3",
-                 fwd_scatter=None, sample_weight=False):
+                 table_rows=None, adam="dense", hist_len=4096, rec_stash=True, gemm="s3", sample_weight=False):
         # sample weights (tf.losses.log_loss's weights=): on with sample_weight (the
         # batch's "weight" entry) or with ModelSpec.pos_weight != 1
         self.weighted = bool(sample_weight) or spec.pos_weight != 1.0
@@ -555,30 +554,6 @@ class CTREngine:
             self.mv_u = z(self.n_rep + self.n_refs, int(_lib.lib().dl_rec_stash_floats(E))) if rec_stash else None
             # hot rows' chunked segment sums (dl_rec_bwd_adam: Zipf rows over many blocks)
             self.hot_ws = z(int(_lib.lib().dl_rec_bwd_workspace_bytes(self.n_refs, E)), dt=torch.uint8)
-        # fwd_rec: the forward reads the cate rows straight from the records (dl_embed_fwd_rec)
-        # instead of gathering the batch's unique rows and reading them back through the
-        # inverse map; only the C replicated cont rows are gathered.  Single-valued fields.
-        # Off by default: bit-identical, but at C2 it measured 444 us against 214 + 123 us for
-        # the gather + indexed pair — the in-register catch-up of every reference at 2
-        # waves/SIMD (169 VGPRs) costs ~190 us that the gather's catch-up hides (253 us with
-        # no rows lagging; scripts/catchup_cost.py).
-        self.fwd_rec = bool(fwd_rec and self.lazy and not M and not rec_stash)
-        # fwd_scatter (opt-in, DLAMD_FWD_SCATTER=1): the gather writes each caught-up row
-        # straight to the references reading it (dl_rec_gather_scatter: FM staging rows,
-        # first-order outputs, x0's deep columns, multi-hot staging rows) and
-        # dl_embed_fwd_staged sums the FM terms per sample from the staging rows — random
-        # 64-B writes in place of the indexed forward's random 64-B reads through the inverse
-        # map.  Measured slower end to end (profiles/r03d: C2 2.45 vs 2.32 ms, the gather
-        # +170 us for the forward's -58 us; C3 gather +830 us for pooling's -95 us): the
-        # per-reference segment walk serialises dependent loads in the gather's waves.
-        if fwd_scatter is None:
-            fwd_scatter = os.environ.get("DLAMD_FWD_SCATTER", "0") != "0"
-        self.fwd_scatter = bool(fwd_scatter and self.lazy and not self.fwd_rec and type(self) is CTREngine)
-        self.fmst = z(self.n_rep + B * S, E) if (self.fwd_scatter and sp.fm) else None
-        # multi-hot staging (scatter form): position l of sample b at row b * multi_width + l
-        mw = sp.multi_width
-        self.mst = z(B * mw, E) if (self.fwd_scatter and M) else None
-        self.mst1 = z(B * mw) if (self.fwd_scatter and M and sp.fm) else None
         # static input slots (graph capture reads from these)
         self.in_label = z(B)
         self.in_cont = z(B, max(sp.C, 1))
@@ -917,7 +892,7 @@ class CTREngine:
         as fused_gather_l0; DLAMD_FUSED_GATHER=0 turns both off."""
         sp = self.spec
         if (os.environ.get("DLAMD_FUSED_GATHER", "1") == "0" or not self.s3 or self.bf or not self.lazy
-                or type(self) is not CTREngine or self.fwd_rec or self.fwd_scatter):
+                or type(self) is not CTREngine):
             return False
         if self.drop:   # the plain first layer reads the dropped x0 (and has the dropout epilogue)
             return False
@@ -1095,30 +1070,6 @@ class CTREngine:
             self._c("embed_fwd", "dl_embed_fwd_rec_flat", C_ref(L), ptr(self.rec), self.rec_ld, self.rec_flags,
                     ptr(self.rows_u), ptr(self.rows_u1) if sp.fm else None, ptr(self.in_cate), ptr(self.in_cont),
                     ptr(self.in_vec), ptr(self.opt), ptr(x0), ptr(self.fm_out), ptr(self.fm_sum), ptr(self.err), s)
-        elif self.fwd_rec:
-            if self.n_rep:   # the replicated FM cont-field rows, caught up, compact
-                self._c("rec_gather", "dl_rec_gather", C_ref(L), ptr(self.rec), self.rec_ld, self.rec_flags, self.n_rep,
-                        ptr(self.idx_uniq), None, 0, 1, ptr(self.hist), self.hist_len, ptr(self.opt),
-                        1 if train else 0, ptr(self.rows_u), ptr(self.rows_u1), None, s)
-            self._c("embed_fwd", "dl_embed_fwd_rec", C_ref(L), ptr(self.rec), self.rec_ld, self.rec_flags,
-                    ptr(self.rows_u), ptr(self.rows_u1) if sp.fm else None, ptr(self.in_cate), ptr(self.in_cont),
-                    ptr(self.in_vec), ptr(self.hist), self.hist_len, ptr(self.opt), 1 if train else 0,
-                    ptr(x0), ptr(self.fm_out), ptr(self.fm_sum), ptr(self.err), s)
-        elif self.fwd_scatter:
-            # rows of the batch (index built by _pre), caught up to the step being taken and
-            # scattered to the references reading them; then the FM sums per sample
-            self._c("rec_gather", "dl_rec_gather_scatter", C_ref(L), ptr(self.rec), self.rec_ld, self.rec_flags,
-                    self.n_rep, ptr(self.idx_uniq), ptr(self.idx_n), B * self.n_slot, ptr(self.idx_off),
-                    ptr(self.idx_refs), ptr(self.hist), self.hist_len, ptr(self.opt), 1 if train else 0,
-                    ptr(self.rows_u), ptr(self.rows_u1), ptr(self.mv_u) if (train and self.mv_u is not None) else None,
-                    ptr(self.fmst), ptr(x0), ptr(self.fm_out), ptr(self.mst), ptr(self.mst1), s)
-            if sp.M:
-                self._c("pool_fwd", "dl_pool_fwd_staged", C_ref(L), ptr(self.mst), ptr(self.mst1), ptr(self.idx_inv),
-                        ptr(self.slot_start), ptr(self.slot_end), sp.M, self.fm_pool_col, ptr(self.x0),
-                        ptr(self.fm_out), ptr(self.cnt_emb), ptr(self.cnt_first), s)
-            self._c("embed_fwd", "dl_embed_fwd_staged", C_ref(L), ptr(self.fmst), ptr(self.rows_u1) if sp.fm else None,
-                    ptr(self.idx_inv), self.n_rep, ptr(self.in_cont), ptr(self.in_vec), ptr(x0), ptr(self.fm_out),
-                    ptr(self.fm_sum), s)
         elif self.lazy:
             # rows of the batch (index built by _pre), caught up to the step being taken
             self._c("rec_gather", "dl_rec_gather", C_ref(L), ptr(self.rec), self.rec_ld, self.rec_flags, self.n_rep,

@@ -138,38 +138,15 @@ int dl_embed_fwd_indexed(const dl_emb_layout* L, const float* rows, const float*
                          const int32_t* inv, int32_t inv_base, const float* cont,
                          const float* vector, float* x0, float* fm_out, float* fm_sum,
                          void* stream);
-/* Staged forward, after dl_rec_gather_scatter: the FM sums per sample over the staging rows
- * fmst (cont fields: compact rows [0, C) x their values; cate field f of sample b: row
- * n_rep + b*S + f), the cont fields' first-order outputs from rows_first[0, C), x0's cont /
- * vector columns, and zeros for every reference without a row (inv < 0: the zero row) —
- * its FM row, first-order output or x0 columns; everything the gather scattered is left. */
-int dl_pool_fwd_staged(const dl_emb_layout* L, const float* mst, const float* mst1, const int32_t* inv,
-                       const int32_t* slot_start, const int32_t* slot_end, int32_t n_slots, int32_t fm_col,
-                       float* x0, float* fm_out, float* cnt_emb, float* cnt_first, void* stream);
-/* dl_pool_fwd_indexed with multi position l of sample b read from the gather's multi-hot
- * staging rows mst[b * multi_width + l] (mst1 the first-order weights); positions without a
- * row (inv < 0: padding) count as none.  Same sums, same order. */
-int dl_embed_fwd_staged(const dl_emb_layout* L, const float* fmst, const float* rows_first, const int32_t* inv,
-                        int32_t n_rep, const float* cont, const float* vector, float* x0, float* fm_out,
-                        float* fm_sum, void* stream);
 
-/* Record forward (single GPU, lazy-exact Adam): dl_embed_fwd with the cate rows read
- * straight from the row records (rec.hip layout) and caught up to step opt[7] - lag in
- * registers (lag 1 in training, 0 for predict), instead of dl_rec_gather writing the
- * batch's unique rows and dl_embed_fwd_indexed reading them back.  The C FM cont-field
- * rows (every sample's) come compact and caught up in rows_rep / rows_rep1 (dl_rec_gather
- * with no unique rows); needs L->cont_rows_compact when there are any.  Outputs are
- * bit-identical to the gather + indexed pair.  Single-valued fields only (multi_width 0). */
-int dl_embed_fwd_rec(const dl_emb_layout* L, const float* rec, int32_t rec_ld, int32_t rec_flags,
-                     const float* rows_rep, const float* rows_rep1, const int64_t* cate,
-                     const float* cont, const float* vector, const float* hist, int32_t hist_len,
-                     const float* opt, int32_t lag, float* x0, float* fm_out, float* fm_sum,
-                     int32_t* err, void* stream);
-/* The record forward on a flushed table (every row caught up to step opt[7]: after
- * dl_rec_flush, before any further update): the plain lookup — each reference reads only its
- * record's first 128-B line (p, and the first-order weight beside it); a row whose stamp is not
- * opt[7] sets DL_STATUS_LAG (the host raises) instead of being read stale.  Same outputs as
- * dl_embed_fwd_rec at lag 0.  rows_rep / rows_rep1: the C FM cont-field rows, compact. */
+/* The record forward on a flushed table (single GPU, lazy-exact Adam; every row caught up to
+ * step opt[7]: after dl_rec_flush, before any further update): dl_embed_fwd with the cate rows
+ * read straight from the row records (rec.hip layout) — each reference reads only its record's
+ * first 128-B line (p, and the first-order weight beside it); a row whose stamp is not opt[7]
+ * sets DL_STATUS_LAG (the host raises) instead of being read stale.  Same outputs as
+ * dl_rec_gather + dl_embed_fwd_indexed at lag 0.  The C FM cont-field rows (every sample's) come
+ * compact in rows_rep / rows_rep1 (dl_rec_gather with no unique rows); needs
+ * L->cont_rows_compact when there are any.  Single-valued fields only (multi_width 0). */
 int dl_embed_fwd_rec_flat(const dl_emb_layout* L, const float* rec, int32_t rec_ld, int32_t rec_flags,
                           const float* rows_rep, const float* rows_rep1, const int64_t* cate,
                           const float* cont, const float* vector, const float* opt, float* x0,
@@ -737,21 +714,6 @@ int dl_rec_gather(const dl_emb_layout* L, const float* rec, int32_t rec_ld, int3
                   int32_t n_rep, const uint32_t* uniq_keys, const int32_t* n_uniq, int64_t max_uniq,
                   int32_t world, const float* hist, int32_t hist_len, const float* opt, int32_t lag,
                   float* rows_u, float* rows_u1, float* mv_u, void* stream);
-/* dl_rec_gather (world 1, every output the same) that ALSO writes each caught-up row to the
- * references reading it, through the batch index's sorted segments (seg_off, sorted_refs of
- * dl_index_build): FM reference (b, f) -> fmst[n_rep + b*S + f][E] and fm_out[b][Cf + f] =
- * w1; deep reference (b, f) -> x0[b][x0_cat_col + f*E] (bf16 when L->x0_bf16); the
- * replicated rows -> fmst[0, n_rep).  Multi-hot reference (b, l) -> mst[b * multi_width + l][E]
- * and mst1[...] = w1 when mst is given (then dl_pool_fwd_staged pools them), else left to
- * the pooling kernels.
- * Random 64-B writes in place of dl_embed_fwd_indexed's random 64-B reads through the
- * inverse map (the forward of models/deepfm_pipeline.py:89-123 reorganised around the
- * batch's unique rows); follow with dl_embed_fwd_staged.  fmst: [n_rep + B*S][E]. */
-int dl_rec_gather_scatter(const dl_emb_layout* L, const float* rec, int32_t rec_ld, int32_t rec_flags,
-                          int32_t n_rep, const uint32_t* uniq_keys, const int32_t* n_uniq, int64_t max_uniq,
-                          const int32_t* seg_off, const int32_t* sorted_refs, const float* hist, int32_t hist_len,
-                          const float* opt, int32_t lag, float* rows_u, float* rows_u1, float* mv_u, float* fmst,
-                          void* x0, float* fm_out, float* mst, float* mst1, void* stream);
 /* Fused backward + Adam: per unique row the ordered segment sum of its references
  * (as dl_embed_bwd_sorted) is applied with step opt[7]'s alpha to the caught-up
  * state of dl_rec_gather (rows_u, rows_u1, mv_u — full arrays, replicated rows

@@ -42,14 +42,16 @@ struct HeadWeight {
   const float* norm;    // {inv_norm, N_nz}
 };
 
-template <bool DROP, bool WEIGHTED = false>
+// EXTRA (dl_head_fwd_bwd_cross): a per-sample term z_extra[b] (the cross network's logit part,
+// cross.hip) is added to the logit before the sigmoid; every output then belongs to the full logit.
+template <bool DROP, bool WEIGHTED = false, bool EXTRA = false>
 __global__ __launch_bounds__(256) void head_kernel(int B, int fm_cols, int H, const float* __restrict__ fm_out,
                                                    int fm_ld, const float* __restrict__ h, int ldh,
                                                    const float* __restrict__ w, const float* __restrict__ label,
                                                    float eps, float inv_batch, float* __restrict__ score,
                                                    float* __restrict__ z_out, float* __restrict__ dz,
                                                    float* __restrict__ dh, float* __restrict__ slab, HeadDrop dr,
-                                                   HeadWeight sw) {
+                                                   HeadWeight sw, const float* __restrict__ z_extra) {
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const uint32_t step = DROP ? drop_step(dr.opt) : 0u;
   const float inv_norm = WEIGHTED ? sw.norm[0] : 0.f;
@@ -87,6 +89,7 @@ __global__ __launch_bounds__(256) void head_kernel(int B, int fm_cols, int H, co
     float4 hh[kAhead][kHeadMaxH4];
     float yy[kAhead];
     float ww[WEIGHTED ? kAhead : 1];
+    float zx[EXTRA ? kAhead : 1];
 #pragma unroll
     for (int i = 0; i < kAhead; ++i) {
       const int b = b0 + i * nwaves;
@@ -116,6 +119,7 @@ __global__ __launch_bounds__(256) void head_kernel(int B, int fm_cols, int H, co
       }
       yy[i] = ok ? label[b] : 0.f;
       if (WEIGHTED) ww[i] = ok ? sw.w_eff[b] : 0.f;
+      if (EXTRA) zx[i] = ok ? z_extra[b] : 0.f;
     }
 #pragma unroll
     for (int i = 0; i < kAhead; ++i) {
@@ -127,7 +131,8 @@ __global__ __launch_bounds__(256) void head_kernel(int B, int fm_cols, int H, co
 #pragma unroll
       for (int k = 0; k < kHeadMaxH4; ++k)
         part += hh[i][k].x * wh[k].x + hh[i][k].y * wh[k].y + hh[i][k].z * wh[k].z + hh[i][k].w * wh[k].w;
-      const float z = wave_sum(part) + bias;
+      float z = wave_sum(part) + bias;
+      if (EXTRA) z += zx[EXTRA ? i : 0];
       const float p = 1.f / (1.f + expf(-z));
       const float y = yy[i];
       const float scale = WEIGHTED ? ww[WEIGHTED ? i : 0] * inv_norm : inv_batch;
@@ -456,18 +461,20 @@ extern "C" int dl_wdl_head_grid(int32_t B) {
   return g < 1 ? 1 : g;
 }
 
-// dl_head_fwd_bwd and its twins: DROP (FM-part dropout, dr) and WEIGHTED (sample weights, sw)
-template <bool DROP, bool WEIGHTED>
+// dl_head_fwd_bwd and its twins: DROP (FM-part dropout, dr), WEIGHTED (sample weights, sw) and
+// EXTRA (a per-sample logit term, z_extra; NULL in every other entry point)
+template <bool DROP, bool WEIGHTED, bool EXTRA = false>
 static int head_launch(const char* name, int32_t B, int32_t fm_cols, int32_t H, const float* fm_out, int32_t fm_ld,
                        const float* h, int32_t ldh, const float* w, const float* label, float eps, float inv_batch,
                        float* score, float* z_out, float* dz, float* dh, float* slab, int32_t slab_blocks,
-                       const HeadDrop& dr, HeadWeight sw, void* stream) {
+                       const HeadDrop& dr, HeadWeight sw, void* stream, const float* z_extra = nullptr) {
   DL_CHECK_ARG(fm_cols >= (DROP ? 1 : 0) && fm_cols <= kHeadMaxFm, "fm_cols %d not in [%d, %d]", fm_cols,
                DROP ? 1 : 0, kHeadMaxFm);
   DL_CHECK_ARG(H > 0 && H <= 4 * 64 * kHeadMaxH4, "H %d > %d", H, 4 * 64 * kHeadMaxH4);
   DL_CHECK_ARG(ldh % 4 == 0 && ldh >= H && ((uintptr_t)h % 16) == 0, "h must be 16-B aligned, ldh %% 4 == 0");
   DL_CHECK_ARG(!fm_cols || fm_out, "fm_out required");
   DL_CHECK_ARG(!WEIGHTED || (sw.w_eff && sw.norm), "w_eff and norm required");
+  DL_CHECK_ARG(!EXTRA || z_extra, "z_extra required");
   if (DROP) {
     DL_CHECK_ARG(dr.F >= 0 && dr.F <= fm_cols, "F %d not in [0, fm_cols %d]", dr.F, fm_cols);
     DL_CHECK_ARG(dr.opt && dr.fm_keep && ((uintptr_t)dr.fm_keep % 16) == 0, "opt and a 16-B aligned fm_keep required");
@@ -478,8 +485,8 @@ static int head_launch(const char* name, int32_t B, int32_t fm_cols, int32_t H, 
   DL_CHECK_ARG(slab_blocks >= grid, "slab needs %d blocks", grid);
   if (B == 0) return 0;
   const size_t lds = 4 * (size_t)(fm_cols + H + 2) * sizeof(float);
-  hipLaunchKernelGGL((head_kernel<DROP, WEIGHTED>), dim3(grid), dim3(256), lds, as_stream(stream), B, fm_cols, H,
-                     fm_out, fm_ld, h, ldh, w, label, eps, inv_batch, score, z_out, dz, dh, slab, dr, sw);
+  hipLaunchKernelGGL((head_kernel<DROP, WEIGHTED, EXTRA>), dim3(grid), dim3(256), lds, as_stream(stream), B, fm_cols,
+                     H, fm_out, fm_ld, h, ldh, w, label, eps, inv_batch, score, z_out, dz, dh, slab, dr, sw, z_extra);
   DL_RETURN_LAUNCH(name);
 }
 
@@ -530,4 +537,23 @@ extern "C" int dl_head_fwd_bwd_fmdrop_weighted(int32_t B, int32_t fm_cols, int32
                                  eps, 0.f, score, z_out, dz, dh, slab, slab_blocks,
                                  head_drop(F, keep_thr1, inv1, keep_thr2, inv2, seed, opt, fm_keep),
                                  HeadWeight{w_eff, norm}, stream);
+}
+
+extern "C" int dl_head_fwd_bwd_cross(int32_t B, int32_t fm_cols, int32_t H, const float* fm_out, int32_t fm_ld,
+                                     const float* h, int32_t ldh, const float* w, const float* label, float eps,
+                                     float inv_batch, const float* z_extra, float* score, float* z_out, float* dz,
+                                     float* dh, float* slab, int32_t slab_blocks, void* stream) {
+  return head_launch<false, false, true>("dl_head_fwd_bwd_cross", B, fm_cols, H, fm_out, fm_ld, h, ldh, w, label, eps,
+                                         inv_batch, score, z_out, dz, dh, slab, slab_blocks, HeadDrop{}, HeadWeight{},
+                                         stream, z_extra);
+}
+
+extern "C" int dl_head_fwd_bwd_cross_weighted(int32_t B, int32_t fm_cols, int32_t H, const float* fm_out,
+                                              int32_t fm_ld, const float* h, int32_t ldh, const float* w,
+                                              const float* label, float eps, const float* w_eff, const float* norm,
+                                              const float* z_extra, float* score, float* z_out, float* dz, float* dh,
+                                              float* slab, int32_t slab_blocks, void* stream) {
+  return head_launch<false, true, true>("dl_head_fwd_bwd_cross_weighted", B, fm_cols, H, fm_out, fm_ld, h, ldh, w,
+                                        label, eps, 0.f, score, z_out, dz, dh, slab, slab_blocks, HeadDrop{},
+                                        HeadWeight{w_eff, norm}, stream, z_extra);
 }

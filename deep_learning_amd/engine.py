@@ -82,14 +82,23 @@ class ModelSpec:
     tf.losses.log_loss's weights= with w_b = weight_b * (1 + (pos_weight - 1) * y_b), which the
     reference leaves at 1); anything but 1 turns the engine's sample weighting on
     (CTREngine(sample_weight=...)).
+    cross_layers: layers of a Deep & Cross network (test_model/DCN.py:73-96) on the tower input of
+    the dnn_pipeline / dnn_cate / dnn_multi / dnn_multi_cate models, its output joining the tower's
+    in the one output layer (parameters cross_layer_%d, cross_bias_%d, cross_res); 0: none.
     """
+
+    CROSS_MODELS = ("dnn_pipeline", "dnn_cate", "dnn_multi", "dnn_multi_cate")
+    CROSS_MAX_LAYERS, CROSS_MAX_IN = 4, 1024     # csrc/cross.hip
 
     def __init__(self, model, C=13, V=0, S=26, E=16, cate_index_size=1000, hidden=(400, 400, 400),
                  multi_ranges=(), Fw=0, lr=0.001, l2=1e-5, decay_steps=10000000, decay_rate=0.9,
                  beta1=0.9, beta2=0.999, eps=1e-8, logloss_eps=1e-7, tower="f32", dropout_keep_deep=None,
-                 dropout_keep_fm=None, pos_weight=1.0):
+                 dropout_keep_fm=None, pos_weight=1.0, cross_layers=0):
         if model not in FAMILIES:
             raise ValueError("unsupported model %r" % model)
+        if int(cross_layers) != cross_layers or cross_layers < 0:
+            raise ValueError("cross_layers must be an integer >= 0, got %r" % (cross_layers,))
+        self.cross_layers = int(cross_layers)
         pos_weight = float(pos_weight)
         if not (math.isfinite(pos_weight) and pos_weight > 0.0):
             raise ValueError("pos_weight must be finite and > 0, got %r" % (pos_weight,))
@@ -130,6 +139,19 @@ class ModelSpec:
                 raise ValueError("dropout_keep_fm values must lie in (0, 1], got %r" % (keep,))
             dropout_keep_fm = keep if fam["fm"] and any(k < 1.0 for k in keep) else None
         self.dropout_keep_fm = dropout_keep_fm
+        if self.cross_layers:
+            if model not in self.CROSS_MODELS:
+                raise ValueError("cross_layers: the cross network joins the tower of %s only, not %s"
+                                 % (", ".join(self.CROSS_MODELS), model))
+            if tower == "bf16":
+                raise ValueError("cross_layers: not supported with tower='bf16' (the cross network reads the f32 "
+                                 "tower input)")
+            if self.dropout and self.dropout[0] < 1.0:
+                raise ValueError("cross_layers: not supported with tower-input dropout (dropout_keep_deep[0] < 1 "
+                                 "rewrites x0 in place; the cross network reads the undropped input)")
+            if self.cross_layers > self.CROSS_MAX_LAYERS or self.deep_in > self.CROSS_MAX_IN:
+                raise ValueError("cross_layers: at most %d layers on at most %d tower-input columns, got %d on %d"
+                                 % (self.CROSS_MAX_LAYERS, self.CROSS_MAX_IN, self.cross_layers, self.deep_in))
 
     @property
     def dropout(self):
@@ -485,7 +507,20 @@ class CTREngine:
             self.fm_drop_desc = _lib.FmDrop(fm_keep=self.fm_keep.data_ptr(), inv1=self._keep_inv(self.fmdrop[0]),
                                             inv2=self._keep_inv(self.fmdrop[1]))
         self.score, self.z, self.dz = z(B), z(B), z(B)
-        self.head_grid = "dl_wdl_head_grid" if self.wdl else "dl_head_grid"   # slab rows per batch size
+        # cross network (ModelSpec.cross_layers, csrc/cross.hip): the parameters as one vector
+        # [c | w_0 .. | b_0 ..] in x0's column order with its Adam moments, the forward's s [B, L]
+        # and z_cross [B], and the backward's per-block partial sums (dl_adam_dense's slab)
+        self.cross = sp.cross_layers
+        if self.cross:
+            if type(self) is not CTREngine:
+                raise ValueError("cross_layers: not supported by %s" % type(self).__name__)
+            self.cross_n = (2 * self.cross + 1) * self.D0
+            self.cw = z(_ru(self.cross_n, 4))
+            self.cm, self.cv = torch.zeros_like(self.cw), torch.zeros_like(self.cw)
+            self.cross_s, self.z_cross = z(B, self.cross), z(B)
+            self.cross_blocks = call_int("dl_cross_grid", B)
+            self.cross_slab = z(self.cross_blocks, self.cross_n)
+        self.head_grid ="dl_wdl_head_grid" if self.wdl else "dl_head_grid"   # slab rows per batch size
         self.head_blocks = call_int(self.head_grid, B)
         self.head_slab = z(self.head_blocks, sp.fm_cols + H + 2)
         self.in_wide = z(B, max(sp.Fw, 1), dt=torch.int64)
@@ -647,6 +682,13 @@ class CTREngine:
         w[:-1] = rng.standard_normal(self.head_n - 1) * g
         w[-1] = rng.standard_normal()
         self.w_head[: self.head_n].copy_(torch.from_numpy(w))
+        if self.cross:
+            # DCN.py:75-79 cross_layer / cross_bias ~ N(0, sqrt(2 / (D + D))); :90-93 the output
+            # layer's cross part ~ N(0, sqrt(2 / (D + H + 1)))
+            D, Lc = self.D0, self.cross
+            v = rng.standard_normal((2 * Lc + 1, D)) * math.sqrt(2.0 / (D + D))
+            v[0] = rng.standard_normal(D) * math.sqrt(2.0 / (D + H + 1))
+            self.cw[: self.cross_n].copy_(torch.from_numpy(v.astype(np.float32).reshape(-1)))
         if getattr(self, "wide_lazy", False):
             self._wide_pack()
         torch.cuda.synchronize()
@@ -712,7 +754,37 @@ class CTREngine:
         w = w[sp.head_ref_index()]
         self.w_head.zero_()
         self.w_head[: self.head_n].copy_(torch.from_numpy(w))
+        if self.cross:
+            self.cw[: self.cross_n].copy_(torch.from_numpy(self._cross_pack(P)))
         torch.cuda.synchronize()
+
+    def _cross_keys(self):
+        """Reference keys of the cross vector's (2L + 1) parts, in its order [c | w_l | b_l]."""
+        Lc = self.cross
+        return ["cross_res"] + ["cross_layer_%d" % l for l in range(Lc)] + ["cross_bias_%d" % l for l in range(Lc)]
+
+    def _cross_pack(self, P):
+        """Reference-layout cross parameters ([D, 1] each, rows in the reference's deep-input
+        order) -> the device vector (x0's column order)."""
+        rows = self.spec.x0_ref_rows()
+        parts = []
+        for k in self._cross_keys():
+            a = np.asarray(P[k], np.float32).reshape(-1)
+            if a.size != self.D0:
+                raise ValueError("%s holds %d values for %d tower-input columns" % (k, a.size, self.D0))
+            parts.append(a[rows])
+        return np.concatenate(parts)
+
+    def _cross_unpack(self, vec):
+        """Inverse of _cross_pack on a device vector: {key: [D, 1] numpy}."""
+        rows = self.spec.x0_ref_rows()
+        v = vec[: self.cross_n].cpu().numpy().reshape(2 * self.cross + 1, self.D0)
+        out = {}
+        for i, k in enumerate(self._cross_keys()):
+            a = np.empty(self.D0, np.float32)
+            a[rows] = v[i]
+            out[k] = a[:, None]
+        return out
 
     def params(self):
         """Export parameters in the reference layout (numpy)."""
@@ -743,15 +815,16 @@ class CTREngine:
     def dense_params(self):
         """The dense parameters (hidden layers, head or wdl weights + bias) in the reference
         layout (numpy); the wide records are caught up first."""
-        return self._export_dense(self.W, self.w_head, self._wide_state()[0], getattr(self, "wb", None))
+        return self._export_dense(self.W, self.w_head, self._wide_state()[0], getattr(self, "wb", None),
+                                  getattr(self, "cw", None))
 
     def dense_state(self):
         """Adam moments of the dense parameters (hidden layers, head / wdl weights) in the
         reference layout: {"m": {key: array}, "v": {key: array}} (tests; the table's are in
         adam_state())."""
         _, wm, wv = self._wide_state()
-        return {"m": self._export_dense(self.Wm, self.hm, wm, getattr(self, "wbm", None)),
-                "v": self._export_dense(self.Wv, self.hv, wv, getattr(self, "wbv", None))}
+        return {"m": self._export_dense(self.Wm, self.hm, wm, getattr(self, "wbm", None), getattr(self, "cm", None)),
+                "v": self._export_dense(self.Wv, self.hv, wv, getattr(self, "wbv", None), getattr(self, "cv", None))}
 
     # ------------------------------------------------------------------ wide records (wdl)
     def _wide_pack(self):
@@ -783,11 +856,11 @@ class CTREngine:
              ptr(self.opt), ptr(self.wsq), ptr(self.wacc), _lib.stream_handle())
         self._wsq_step = self.steps
 
-    def _export_dense(self, Ws, head, ww, wb):
+    def _export_dense(self, Ws, head, ww, wb, cross=None):
         """Augmented hidden-layer matrices (bias row, x0 column order), the permuted head
-        vector and the wdl weights -> reference keys and layouts."""
+        vector, the wdl weights and the cross vector -> reference keys and layouts."""
         sp = self.spec
-        P = {}
+        P = self._cross_unpack(cross) if cross is not None else {}
         dims = [self.D0] + sp.hidden
         for l in range(len(sp.hidden)):
             Wi = Ws[l].cpu().numpy()
@@ -927,6 +1000,8 @@ class CTREngine:
         DLAMD_FUSED_GATHER=0 turns it off."""
         sp = self.spec
         if os.environ.get("DLAMD_FUSED_GATHER", "1") == "0" or not self.s3 or self.bf or sp.M:
+            return False
+        if self.cross:   # the cross network reads x0's deep columns, which the fused forms leave unwritten
             return False
         pl = getattr(self, "p_plane", None)
         return (pl is not None and self.cat_col == 0 and sp.E in (8, 16, 32, 64) and 0 < sp.S <= 40
@@ -1193,6 +1268,16 @@ class CTREngine:
                     self.head_blocks, sp.F, self._keep_thr(k1), self._keep_inv(k1), self._keep_thr(k2),
                     self._keep_inv(k2), self.seed & 0xFFFFFFFFFFFFFFFF, ptr(self.opt), ptr(self.fm_keep), s)
             return
+        if self.cross:
+            # x0 is complete here (in lazy training the first layer's fused row gather wrote its
+            # deep columns): s and z_cross, then the head with z_cross added to the logit
+            self._c("cross_fwd", "dl_cross_fwd", B, self.D0, self.cross, ptr(self.x0), self.in_ld[0], ptr(self.cw),
+                    ptr(self.cross_s), ptr(self.z_cross), s)
+            self._c("head", "dl_head_fwd_bwd_cross" + sw, B, sp.fm_cols, H, ptr(self.fm_out), self.fm_ld,
+                    ptr(self.h[-1]), self.h_ld[-1], ptr(self.w_head), ptr(self.in_label), sp.logloss_eps, *scale,
+                    ptr(self.z_cross), ptr(self.score), ptr(self.z), ptr(self.dz), ptr(self.dh[-1]),
+                    ptr(self.head_slab), self.head_blocks, s)
+            return
         self._c("head", "dl_head_fwd_bwd" + sw, B, sp.fm_cols, H, ptr(self.fm_out), self.fm_ld, ptr(self.h[-1]),
              self.h_ld[-1], ptr(self.w_head), ptr(self.in_label), sp.logloss_eps, *scale,
              ptr(self.score), ptr(self.z), ptr(self.dz), ptr(self.dh[-1]), ptr(self.head_slab),
@@ -1389,6 +1474,12 @@ class CTREngine:
                 dw(l)
                 dx(l)
                 adam(l)
+        if self.cross:
+            # gemm_dx_l0 has written dx0 (the embedding columns of x0, from column cat_col); the cross
+            # network's share is added before the embedding backward reads it
+            self._c("cross_bwd", "dl_cross_bwd", B, self.D0, self.cross, ptr(self.x0), self.in_ld[0], ptr(self.cw),
+                    ptr(self.cross_s), ptr(self.dz), ptr(self.dx0), self.dx_ld, self.cat_col, self.dx_cols,
+                    ptr(self.cross_slab), self.cross_blocks, s)
         if part == "all":
             self._train_back(B, s, L)
 
@@ -1460,6 +1551,12 @@ class CTREngine:
         self._c("adam_head", "dl_adam_dense", ptr(self.w_head), ptr(self.hm), ptr(self.hv), ptr(self.head_slab),
                 hb, sp.fm_cols + H + 2, self.head_n, sp.l2 if sp.head_l2 else 0.0,
                 self.head_n - 1 if sp.head_l2 else 0, ptr(self.opt), ptr(self.w_head_prev), ptr(self.opt[8:]), s)
+        if self.cross:
+            # cross Adam: L2 on c, the output layer's cross part (DCN.py:104: the whole projection),
+            # its sum of squares joining the head's in the step's regulariser sum
+            self._c("adam_cross", "dl_adam_dense", ptr(self.cw), ptr(self.cm), ptr(self.cv), ptr(self.cross_slab),
+                    call_int("dl_cross_grid", B), self.cross_n, self.cross_n, sp.l2, self.D0, ptr(self.opt), None,
+                    ptr(self.opt[8:]), s)
         if self.lazy:
             return
         if sp.fm:

@@ -13,6 +13,9 @@ pos_weight=2.5 weights the positives' loss terms and weight_key=NAME reads a per
 from the float [1] TFRecord feature NAME (tf.losses.log_loss's weights=, which the reference leaves
 at 1); with weight_key, evaluation's logloss and calibration are weighted too.
 
+cross_layers=N (dnn_pipeline, dnn_cate, dnn_multi, dnn_multi_cate) adds an N-layer Deep & Cross
+network on the tower input, its output joining the tower's in the output layer.
+
 Two more overrides choose what evaluation reports (deep_learning_amd/metrics.py); without them
 the output is the reference's: eval_metrics=auc,gauc,logloss,calibration (default auc) and
 gauc_slot=K, the cate_feats column whose id groups the samples for GAUC (the user-id slot).
@@ -73,6 +76,8 @@ class ModelParams:
                 if not v:
                     raise SystemExit("weight_key= needs the name of a float [1] TFRecord feature")
                 self.weight_key = v
+            elif k == "cross_layers":   # a cross network beside the dnn_* tower, stored only when given
+                self.cross_layers = check_cross_layers(v, self.alg_name)
             else:
                 raise SystemExit("unknown override %s" % k)
         (self.cont_field_size, self.vector_feats_size, self.cate_field_size, self.multi_feats_size,
@@ -92,6 +97,22 @@ def check_pos_weight(v):
     if not (w > 0.0 and w != float("inf")):
         raise SystemExit("pos_weight=%s must be finite and > 0" % v)
     return w
+
+
+def check_cross_layers(v, alg_name):
+    """cross_layers=N as an int; refuses (SystemExit) anything but an integer >= 0, and N > 0 for a
+    model other than the dnn_* ones or beyond what the engine takes."""
+    from .engine import ModelSpec
+    try:
+        n = int(v)
+    except ValueError:
+        raise SystemExit("cross_layers=%s is not an integer" % v)
+    if n < 0 or n > ModelSpec.CROSS_MAX_LAYERS:
+        raise SystemExit("cross_layers=%s must lie in [0, %d]" % (v, ModelSpec.CROSS_MAX_LAYERS))
+    if n and alg_name not in ModelSpec.CROSS_MODELS:
+        raise SystemExit("cross_layers=%s: the cross network joins the tower of %s only, not %s"
+                         % (v, ", ".join(ModelSpec.CROSS_MODELS), alg_name))
+    return n
 
 
 def check_eval_options(eval_metrics, gauc_slot, cate_field_size):

@@ -52,6 +52,8 @@ def _spec_from_args(model, args):
         kw.update(dropout_keep_fm=[float(k) for k in keep_fm])
     if getattr(args, "pos_weight", None) is not None:   # local_run's pos_weight= (stored only when given)
         kw.update(pos_weight=float(args.pos_weight))
+    if getattr(args, "cross_layers", None) is not None:   # local_run's cross_layers= (stored only when given)
+        kw.update(cross_layers=int(args.cross_layers))
     return ModelSpec(model, **kw)
 
 
@@ -224,6 +226,8 @@ def _adam_state(eng):
     out = {"adam/opt": eng.opt.cpu().numpy(), "adam/steps": np.array([eng.steps])}
     out.update({"adam/table_" + k: v for k, v in eng.adam_state().items()})
     out["adam/hm"], out["adam/hv"] = eng.hm.cpu().numpy(), eng.hv.cpu().numpy()
+    if eng.cross:   # the cross vector's moments, in the device layout (engine.py _cross_pack)
+        out["adam/cm"], out["adam/cv"] = eng.cm.cpu().numpy(), eng.cv.cpu().numpy()
     for l in range(len(eng.W)):
         out["adam/Wm%d" % l] = eng.Wm[l].cpu().numpy()
         out["adam/Wv%d" % l] = eng.Wv[l].cpu().numpy()
@@ -236,6 +240,9 @@ def _load_adam_state(eng, d):
     eng.set_adam_state({k[len("adam/table_"):]: d[k] for k in d.files if k.startswith("adam/table_")})
     eng.hm.copy_(torch.from_numpy(d["adam/hm"]))
     eng.hv.copy_(torch.from_numpy(d["adam/hv"]))
+    if eng.cross:
+        eng.cm.copy_(torch.from_numpy(d["adam/cm"]))
+        eng.cv.copy_(torch.from_numpy(d["adam/cv"]))
     for l in range(len(eng.W)):
         eng.Wm[l].copy_(torch.from_numpy(d["adam/Wm%d" % l]))
         eng.Wv[l].copy_(torch.from_numpy(d["adam/Wv%d" % l]))

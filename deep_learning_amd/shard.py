@@ -177,6 +177,9 @@ class ShardedCTREngine(CTREngine):
         if spec.dropout_keep_fm:
             raise ValueError("dropout_keep_fm: not supported by ShardedCTREngine (the mask is indexed by the "
                              "local row number; a sharded batch needs global rows)")
+        if spec.cross_layers:
+            raise ValueError("cross_layers: not supported by ShardedCTREngine (the cross parameters' gradients "
+                             "are not part of the flat all-reduce)")
         # the status ring holds 4 reports (slot k & 3) and the host reads report k only after
         # k + lag was submitted: lag <= 3, or report k + 4 overwrites k before it is read
         if not 0 <= int(lag) <= 3:

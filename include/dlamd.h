@@ -460,6 +460,37 @@ int dl_head_grid(int32_t B);
 /* Blocks (= slab rows) of dl_wdl_head_fwd_bwd[_bf16] for batch B. */
 int dl_wdl_head_grid(int32_t B);
 
+/* ------------------------------------------------------------------------
+ * Cross network of Deep & Cross beside the dnn_* tower (test_model/DCN.py:73-96), on the
+ * tower input x0 [B, ld] (its first D columns), L layers:
+ *   x_0 = x0;  s_l = x_l . w_l;  x_{l+1} = x0 * s_l + b_l + x_l  (l < L);  z_cross = x_L . c
+ * params: (2L + 1) vectors of D floats, [c | w_0 .. w_{L-1} | b_0 .. b_{L-1}], in x0's column
+ * order.  D <= 1024 and 1 <= L <= 4; anything else is refused.
+ * dl_cross_fwd writes s [B, L] and z_cross [B] (x_L is never stored: HBM traffic is one read of
+ * x0).  dl_cross_bwd rebuilds every x_l from x0, s and b, and with g_L = dz c, top down,
+ *   t_l = g_{l+1} . x0;  dw_l += t_l x_l;  db_l += g_{l+1};  dx0 += g_{l+1} s_l;  g_l = g_{l+1} + t_l w_l
+ * then dx0 += g_0 and dc += dz x_L.  dx0 [B, dx_ld] holds x0's columns [dx_col0, dx_col0 + dx_cols)
+ * only (the embedding columns) and is added into; the batch sums of (dc, dw_l, db_l) are left as
+ * per-block partials slab[block][(2L + 1) D] in the layout of params (dl_cross_grid(B) blocks, at
+ * most 512; dl_adam_dense sums them in slab order).  No atomics: the same inputs give the same
+ * bits on every run.  dl_head_fwd_bwd_cross[_weighted]: dl_head_fwd_bwd[_weighted] with
+ * z_extra[b] (z_cross) added to the logit before the sigmoid. */
+int dl_cross_grid(int32_t B);
+int dl_cross_fwd(int32_t B, int32_t D, int32_t L, const float* x0, int32_t ld, const float* params,
+                 float* s, float* z_cross, void* stream);
+int dl_cross_bwd(int32_t B, int32_t D, int32_t L, const float* x0, int32_t ld, const float* params,
+                 const float* s, const float* dz, float* dx0, int32_t dx_ld, int32_t dx_col0,
+                 int32_t dx_cols, float* slab, int32_t slab_rows, void* stream);
+int dl_head_fwd_bwd_cross(int32_t B, int32_t fm_cols, int32_t H, const float* fm_out, int32_t fm_ld,
+                          const float* h, int32_t ldh, const float* w, const float* label,
+                          float eps, float inv_batch, const float* z_extra, float* score, float* z_out,
+                          float* dz, float* dh, float* slab, int32_t slab_blocks, void* stream);
+int dl_head_fwd_bwd_cross_weighted(int32_t B, int32_t fm_cols, int32_t H, const float* fm_out, int32_t fm_ld,
+                                   const float* h, int32_t ldh, const float* w, const float* label,
+                                   float eps, const float* w_eff, const float* norm, const float* z_extra,
+                                   float* score, float* z_out, float* dz, float* dh, float* slab,
+                                   int32_t slab_blocks, void* stream);
+
 /* Wide&Deep cross logit, forward and backward fused (models/wdl.py:225-275):
  * z = sum_f w[wide_f] + sum_j w[Fw+j] h_j + bias[0] (w = wdl_weights [w_rows]; the
  * deep-output rows Fw..Fw+H alias wide ids); sigmoid + eps-log-loss as dl_head_fwd_bwd.

@@ -1117,11 +1117,25 @@ class CTREngine:
         return bool(self.drop) and self.drop[layer] < 1.0
 
     def _forward(self, B, s, train=False):
+        """The forward's launches: the embedding front, the deep tower, the head (and its loss
+        gradient dz, dh[-1])."""
+        fused = self._embed_front(B, s, train)
+        if train and self._dropping(0):
+            # input dropout on x0's deep_in columns (the bias "ones" column stays); predict never drops
+            self._c("drop_x0", "dl_dropout_apply", ptr(self.x0), B, self.D0, self.in_ld[0], *self._drop_args(0),
+                    None, s)
+        self._tower_fwd(B, s, train, fused)
+        self._head(B, s, train)
+
+    def _embed_front(self, B, s, train):
+        """The embedding lookups into x0 and the FM part (pooled, planes, flushed, lazy or dense
+        tables).  Returns how the first tower layer gathers the deep rows itself: False (it
+        does not), True / "tab" (predict on planes) or "rows" (lazy training)."""
         sp = self.spec
         L = self.layout
         L.batch = B
         x0 = self.x0b if self.x0_direct else self.x0
-        fused = False   # the deep lookup inside the first tower layer (predict on planes only)
+        fused = False   # the deep lookup inside the first tower layer
         if sp.M and not self.lazy:  # pooled vectors must be in x0 before the FM second order reads them
             self._c("pool_fwd", "dl_pool_fwd", C_ref(L), ptr(self.table), ptr(self.first) if sp.fm else None,
                  ptr(self.in_cate), sp.S, ptr(self.slot_start), ptr(self.slot_end), sp.M, self.fm_pool_col,
@@ -1170,11 +1184,14 @@ class CTREngine:
             self._c("embed_fwd", "dl_embed_fwd", C_ref(L), ptr(self.table), ptr(self.first), ptr(self.in_cate),
                     ptr(self.in_cont), ptr(self.in_vec), ptr(x0), ptr(self.fm_out), ptr(self.fm_sum),
                     ptr(self.err), s)
+        return fused
+
+    def _tower_fwd(self, B, s, train=False, fused=False):
+        """The deep tower's forward from x0 (f32 / three-plane split on bf16 MFMA / bf16 tower),
+        shared with ShardedCTREngine.  fused: the first layer gathers the deep rows itself
+        (_embed_front); train: the dropout epilogue where a layer's output drops."""
+        sp = self.spec
         nl = len(sp.hidden)
-        if train and self._dropping(0):
-            # input dropout on x0's deep_in columns (the bias "ones" column stays); predict never drops
-            self._c("drop_x0", "dl_dropout_apply", ptr(self.x0), B, self.D0, self.in_ld[0], *self._drop_args(0),
-                    None, s)
         if self.bf:
             # bf16 tower: x0 -> bf16, ReLU layers on bf16 MFMA (fp32 accumulate), the last layer's
             # output kept fp32 for the fp32 head / wide cross logit (config C5)
@@ -1231,6 +1248,11 @@ class CTREngine:
                 self._c("gemm_fwd_l%d" % l, "dl_gemm_f32", 0, 0, B, hdim, self.in_ld[l], ptr(x), self.in_ld[l],
                         ptr(self.W[l]), self.out_ld[l], ptr(self.h[l]), self.h_ld[l], 1, None, 0, 1, 0, s)
                 x = self.h[l]
+
+    def _head(self, B, s, train):
+        """The output layer, the loss and its gradients dz and dh[-1]: the wdl cross logit (wide
+        rows dense or lazy), or the FM / deep_res head (plain, FM-part dropout, cross network)."""
+        sp = self.spec
         H = sp.hidden[-1]
         # the loss scale: the host constant 1 / B, or in a weighted training step the *_weighted
         # twins' (w_eff, norm) — predict ignores the weights
@@ -1366,114 +1388,27 @@ class CTREngine:
             self._c("drop_dh", "dl_dropout_apply", ptr(self.dh[-1]), B, sp.hidden[-1], self.h_ld[-1],
                     *self._drop_args(nl), None, s)
         dws = self._dw_splits(B, fixed="DLAMD_DW_SPLITS" in os.environ)
-        if self.bf and not self.wdl:      # the wdl head writes its bf16 dY itself
-            self._c("cast_dh", "dl_cast_bf16", ptr(self.dh[-1]), B, self.h_ld[-1], self.h_ld[-1], ptr(self.dhb[-1]),
-                    self.h_ld[-1], s)
-        def dw(l):   # the weight gradient of layer l (split-K slabs into w_slab)
-            hdim, stride = sp.hidden[l], self.in_ld[l] * self.out_ld[l]
-            splits = dws[l]
-            if self.bf:
-                # dW = X^T dY straight from the batch-major bf16 activations and gradients
-                # (transposing LDS reads inside the kernel: no X^T / dY^T copies)
-                xl = self.x0b if l == 0 else self.hb[l - 1]
-                self._c("gemm_dw_l%d" % l, "dl_gemm_bf16", 1, 0, self.in_ld[l], hdim, B, ptr(xl), self.in_ld[l],
-                        ptr(self.dhb[l]), self.h_ld[l], ptr(self.w_slabs[l]), self.out_ld[l], 0, 3, None, 0, splits,
-                        stride, s)
-            elif self.s3:   # dW = X^T dY (split-K slabs over the batch)
-                xin = self.x0 if l == 0 else self.h[l - 1]
-                i, o = self.in_ld[l], self.out_ld[l]
-                # (a width that is no multiple of 4 is rounded up for the TN kernel: dh's pad columns
-                # are zero and stay so, so are their weight gradients)
-                self._c("gemm_dw_l%d" % l, "dl_gemm_s3_tn", i, _ru(hdim, 4), B, ptr(xin), i, ptr(self.dh[l]), self.h_ld[l],
-                        ptr(self.w_slabs[l]), o, splits, stride, s)
-            else:
-                xin = self.x0 if l == 0 else self.h[l - 1]
-                self._c("gemm_dw_l%d" % l, "dl_gemm_f32", 1, 0, self.in_ld[l], hdim, B, ptr(xin), self.in_ld[l],
-                        ptr(self.dh[l]), self.h_ld[l], ptr(self.w_slab), self.out_ld[l], 3, None, 0, splits, stride, s)
-
-        def dx(l):   # the input gradient of layer l (ReluGrad by the layer below; l = 0: dx0 in f32)
-            if self.bf:
-                if l > 0:   # dX = dY . W^T, ReluGrad by the bf16 activations, bf16 out
-                    self._c("gemm_dx_l%d" % l, "dl_gemm_bf16", 0, 1, B, sp.hidden[l - 1], self.out_ld[l],
-                            ptr(self.dhb[l]), self.h_ld[l], ptr(self.Wb[l]), self.out_ld[l], ptr(self.dhb[l - 1]),
-                            self.h_ld[l - 1], 1, 2, ptr(self.hb[l - 1]), self.h_ld[l - 1], 1, 0, s)
-                else:       # dx0 stays fp32 for the embedding backward
-                    self._c("gemm_dx_l0", "dl_gemm_bf16", 0, 1, B, self.dx_cols, self.out_ld[0], ptr(self.dhb[0]),
-                            self.h_ld[0], ptr(self.Wb[0]), self.out_ld[0], ptr(self.dx0), self.dx_ld, 0, 0, None, 0,
-                            1, 0, s)
-            elif self.s3:   # dX = dY W^T with ReluGrad
-                i, o = self.in_ld[l], self.out_ld[l]
-                if l > 0 and self._dropping(l):   # ReluGrad and the keep bit from the combined bitmask, times 1/keep
-                    self._c("gemm_dx_l%d" % l, "dl_gemm_s3_nt_drop", B, sp.hidden[l - 1], o, ptr(self.dh[l]),
-                            self.h_ld[l], ptr(self.Wp[l]), o, i * o, ptr(self.dh[l - 1]), self.h_ld[l - 1], 3,
-                            None, 0, ptr(self.hbits[l - 1]), self.hbits_ld[l - 1], *self._drop_args(l), s)
-                elif l > 0 and self.relu_bits:   # ReluGrad from the forward's sign bitmask
-                    self._c("gemm_dx_l%d" % l, "dl_gemm_s3_nt_bits", B, sp.hidden[l - 1], o, ptr(self.dh[l]),
-                            self.h_ld[l], ptr(self.Wp[l]), o, i * o, ptr(self.dh[l - 1]), self.h_ld[l - 1], 3,
-                            None, 0, ptr(self.hbits[l - 1]), self.hbits_ld[l - 1], s)
-                elif l > 0:
-                    self._c("gemm_dx_l%d" % l, "dl_gemm_s3_nt", B, sp.hidden[l - 1], o, ptr(self.dh[l]),
-                            self.h_ld[l], ptr(self.Wp[l]), o, i * o, ptr(self.dh[l - 1]), self.h_ld[l - 1], 2,
-                            ptr(self.h[l - 1]), self.h_ld[l - 1], s)
-                else:
-                    self._c("gemm_dx_l0", "dl_gemm_s3_nt", B, self.dx_cols, o, ptr(self.dh[0]), self.h_ld[0],
-                            ptr(self.Wp[0]), o, i * o, ptr(self.dx0), self.dx_ld, 0, None, 0, s)
-                    if self._dropping(0):   # the input dropout's mask on the embedding columns' gradient
-                        self._c("drop_dx0", "dl_dropout_apply", ptr(self.dx0), B, self.dx_cols, self.dx_ld,
-                                *self._drop_args(0), None, s)
-            else:
-                self._c("transpose_l%d" % l, "dl_transpose_f32", ptr(self.W[l]), self.in_ld[l], self.out_ld[l],
-                        self.out_ld[l], ptr(self.Wt), self.in_ld[l], s)
-                if l > 0:
-                    self._c("gemm_dx_l%d" % l, "dl_gemm_f32", 0, 0, B, sp.hidden[l - 1], self.out_ld[l],
-                            ptr(self.dh[l]), self.h_ld[l], ptr(self.Wt), self.in_ld[l], ptr(self.dh[l - 1]),
-                            self.h_ld[l - 1], 2, ptr(self.h[l - 1]), self.h_ld[l - 1], 1, 0, s)
-                else:
-                    self._c("gemm_dx_l0", "dl_gemm_f32", 0, 0, B, self.dx_cols, self.out_ld[0], ptr(self.dh[0]),
-                            self.h_ld[0], ptr(self.Wt), self.in_ld[0], ptr(self.dx0), self.dx_ld, 0, None, 0, 1, 0, s)
-
-        def adam(l):
-            # regulariser on every hidden weight matrix: wdl L2 (wdl.py:272-275), dnn L1 (dnn.py:88-90);
-            # bias row excluded
-            stride = self.in_ld[l] * self.out_ld[l]
-            nsplit = _num_splits(B, dws[l], 64 if (self.bf or self.s3) else 16)
-            reg = sp.hidden_reg
-            l2, l2n = (sp.l2, ([self.D0] + sp.hidden)[l] * self.out_ld[l]) if reg else (0.0, 0)
-            if self.s3 or self.bf:   # the update writes the GEMM operand copies of W and W^T itself
-                self._c("adam_dense_l%d" % l, "dl_adam_dense_split3" if self.s3 else "dl_adam_dense_bf16", ptr(self.W[l]), ptr(self.Wm[l]), ptr(self.Wv[l]),
-                        ptr(self.w_slabs[l]), nsplit, stride, self.in_ld[l], self.out_ld[l], l2, l2n,
-                        1 if reg == "l1" else 0, ptr(self.opt), ptr(self.opt[8:]) if reg else None,
-                        ptr(self.Wp[l] if self.s3 else self.Wb[l]), ptr(self.WTp[l] if self.s3 else self.WbT[l]), s)
-                return
-            self._c("adam_dense_l%d" % l, "dl_adam_dense_reg", ptr(self.W[l]), ptr(self.Wm[l]), ptr(self.Wv[l]),
-                    ptr(self.w_slab), nsplit, stride, stride, l2, l2n, 1 if reg == "l1" else 0, ptr(self.opt),
-                    None, ptr(self.opt[8:]) if reg else None, s)
-            self._refresh_wb(l, s)
-
-        if self._adam_fused():
-            # every layer's weight and input gradients, then one launch for the dense Adams (each
-            # layer's W planes are read by its dX first; nothing else reads W before the next step)
-            for l in reversed(range(nl)):
-                dw(l)
-                dx(l)
-            reg = sp.hidden_reg
+        self._cast_dh(B, s)
+        fused = self._adam_fused()
+        for l in reversed(range(nl)):
+            # fused: every layer's weight and input gradients, then one launch for the dense Adams
+            # (each layer's W planes are read by its dX first; nothing else reads W before the next
+            # step); else each layer's Adam after its input gradient
+            self._tower_dw(l, B, dws[l], self.w_slabs[l], s)
+            self._tower_dx(l, B, s)
+            if not fused:
+                self._tower_adam(l, self.w_slabs[l], _num_splits(B, dws[l], 64 if (self.bf or self.s3) else 16), s)
+        if fused:
             lay = (_lib.AdamLayer * nl)()
             for l in range(nl):
-                stride = self.in_ld[l] * self.out_ld[l]
-                l2, l2n = (sp.l2, ([self.D0] + sp.hidden)[l] * self.out_ld[l]) if reg else (0.0, 0)
-                lay[l] = _lib.AdamLayer(ptr(self.W[l]), ptr(self.Wm[l]), ptr(self.Wv[l]), ptr(self.w_slabs[l]), stride,
-                                        l2n, ptr(self.opt[8:]) if reg else None,
+                l2, l2n, l1, reg_sum = self._layer_reg(l)
+                lay[l] = _lib.AdamLayer(ptr(self.W[l]), ptr(self.Wm[l]), ptr(self.Wv[l]), ptr(self.w_slabs[l]),
+                                        self.in_ld[l] * self.out_ld[l], l2n, reg_sum,
                                         ptr(self.Wp[l] if self.s3 else self.Wb[l]),
                                         ptr(self.WTp[l] if self.s3 else self.WbT[l]),
-                                        _num_splits(B, dws[l], 64), self.in_ld[l], self.out_ld[l],
-                                        1 if reg == "l1" else 0, l2, 0)
+                                        _num_splits(B, dws[l], 64), self.in_ld[l], self.out_ld[l], l1, l2, 0)
             self._adam_lay = lay   # kept alive: a captured graph's kernel arguments were copied at launch
             self._c("adam_dense", "dl_adam_dense_layers", nl, C_ref(lay), 3 if self.s3 else 1, ptr(self.opt), s)
-        else:
-            for l in reversed(range(nl)):
-                dw(l)
-                dx(l)
-                adam(l)
         if self.cross:
             # gemm_dx_l0 has written dx0 (the embedding columns of x0, from column cat_col); the cross
             # network's share is added before the embedding backward reads it
@@ -1482,6 +1417,103 @@ class CTREngine:
                     ptr(self.cross_slab), self.cross_blocks, s)
         if part == "all":
             self._train_back(B, s, L)
+
+    def _cast_dh(self, B, s):
+        """The bf16 tower's copy of the head's dh[-1] (the wdl head writes its bf16 dY itself)."""
+        if self.bf and not self.wdl:
+            self._c("cast_dh", "dl_cast_bf16", ptr(self.dh[-1]), B, self.h_ld[-1], self.h_ld[-1], ptr(self.dhb[-1]),
+                    self.h_ld[-1], s)
+
+    # The tower's backward, one layer at a time; ShardedCTREngine launches the same methods (its
+    # weight gradients into its one slab, its Adam from the all-reduced flat gradient).
+    def _tower_dw(self, l, B, splits, slab, s):
+        """The weight gradient of layer l: `splits` split-K slabs over the batch into `slab`."""
+        sp = self.spec
+        hdim, stride = sp.hidden[l], self.in_ld[l] * self.out_ld[l]
+        if self.bf:
+            # dW = X^T dY straight from the batch-major bf16 activations and gradients
+            # (transposing LDS reads inside the kernel: no X^T / dY^T copies)
+            xl = self.x0b if l == 0 else self.hb[l - 1]
+            self._c("gemm_dw_l%d" % l, "dl_gemm_bf16", 1, 0, self.in_ld[l], hdim, B, ptr(xl), self.in_ld[l],
+                    ptr(self.dhb[l]), self.h_ld[l], ptr(slab), self.out_ld[l], 0, 3, None, 0, splits,
+                    stride, s)
+        elif self.s3:   # dW = X^T dY (split-K slabs over the batch)
+            xin = self.x0 if l == 0 else self.h[l - 1]
+            i, o = self.in_ld[l], self.out_ld[l]
+            # (a width that is no multiple of 4 is rounded up for the TN kernel: dh's pad columns
+            # are zero and stay so, so are their weight gradients)
+            self._c("gemm_dw_l%d" % l, "dl_gemm_s3_tn", i, _ru(hdim, 4), B, ptr(xin), i, ptr(self.dh[l]), self.h_ld[l],
+                    ptr(slab), o, splits, stride, s)
+        else:
+            xin = self.x0 if l == 0 else self.h[l - 1]
+            self._c("gemm_dw_l%d" % l, "dl_gemm_f32", 1, 0, self.in_ld[l], hdim, B, ptr(xin), self.in_ld[l],
+                    ptr(self.dh[l]), self.h_ld[l], ptr(slab), self.out_ld[l], 3, None, 0, splits, stride, s)
+
+    def _tower_dx(self, l, B, s):
+        """The input gradient of layer l (ReluGrad by the layer below; l = 0: dx0 in f32)."""
+        sp = self.spec
+        if self.bf:
+            if l > 0:   # dX = dY . W^T, ReluGrad by the bf16 activations, bf16 out
+                self._c("gemm_dx_l%d" % l, "dl_gemm_bf16", 0, 1, B, sp.hidden[l - 1], self.out_ld[l],
+                        ptr(self.dhb[l]), self.h_ld[l], ptr(self.Wb[l]), self.out_ld[l], ptr(self.dhb[l - 1]),
+                        self.h_ld[l - 1], 1, 2, ptr(self.hb[l - 1]), self.h_ld[l - 1], 1, 0, s)
+            else:       # dx0 stays fp32 for the embedding backward
+                self._c("gemm_dx_l0", "dl_gemm_bf16", 0, 1, B, self.dx_cols, self.out_ld[0], ptr(self.dhb[0]),
+                        self.h_ld[0], ptr(self.Wb[0]), self.out_ld[0], ptr(self.dx0), self.dx_ld, 0, 0, None, 0,
+                        1, 0, s)
+        elif self.s3:   # dX = dY W^T with ReluGrad
+            i, o = self.in_ld[l], self.out_ld[l]
+            if l > 0 and self._dropping(l):   # ReluGrad and the keep bit from the combined bitmask, times 1/keep
+                self._c("gemm_dx_l%d" % l, "dl_gemm_s3_nt_drop", B, sp.hidden[l - 1], o, ptr(self.dh[l]),
+                        self.h_ld[l], ptr(self.Wp[l]), o, i * o, ptr(self.dh[l - 1]), self.h_ld[l - 1], 3,
+                        None, 0, ptr(self.hbits[l - 1]), self.hbits_ld[l - 1], *self._drop_args(l), s)
+            elif l > 0 and self.relu_bits:   # ReluGrad from the forward's sign bitmask
+                self._c("gemm_dx_l%d" % l, "dl_gemm_s3_nt_bits", B, sp.hidden[l - 1], o, ptr(self.dh[l]),
+                        self.h_ld[l], ptr(self.Wp[l]), o, i * o, ptr(self.dh[l - 1]), self.h_ld[l - 1], 3,
+                        None, 0, ptr(self.hbits[l - 1]), self.hbits_ld[l - 1], s)
+            elif l > 0:
+                self._c("gemm_dx_l%d" % l, "dl_gemm_s3_nt", B, sp.hidden[l - 1], o, ptr(self.dh[l]),
+                        self.h_ld[l], ptr(self.Wp[l]), o, i * o, ptr(self.dh[l - 1]), self.h_ld[l - 1], 2,
+                        ptr(self.h[l - 1]), self.h_ld[l - 1], s)
+            else:
+                self._c("gemm_dx_l0", "dl_gemm_s3_nt", B, self.dx_cols, o, ptr(self.dh[0]), self.h_ld[0],
+                        ptr(self.Wp[0]), o, i * o, ptr(self.dx0), self.dx_ld, 0, None, 0, s)
+                if self._dropping(0):   # the input dropout's mask on the embedding columns' gradient
+                    self._c("drop_dx0", "dl_dropout_apply", ptr(self.dx0), B, self.dx_cols, self.dx_ld,
+                            *self._drop_args(0), None, s)
+        else:
+            self._c("transpose_l%d" % l, "dl_transpose_f32", ptr(self.W[l]), self.in_ld[l], self.out_ld[l],
+                    self.out_ld[l], ptr(self.Wt), self.in_ld[l], s)
+            if l > 0:
+                self._c("gemm_dx_l%d" % l, "dl_gemm_f32", 0, 0, B, sp.hidden[l - 1], self.out_ld[l],
+                        ptr(self.dh[l]), self.h_ld[l], ptr(self.Wt), self.in_ld[l], ptr(self.dh[l - 1]),
+                        self.h_ld[l - 1], 2, ptr(self.h[l - 1]), self.h_ld[l - 1], 1, 0, s)
+            else:
+                self._c("gemm_dx_l0", "dl_gemm_f32", 0, 0, B, self.dx_cols, self.out_ld[0], ptr(self.dh[0]),
+                        self.h_ld[0], ptr(self.Wt), self.in_ld[0], ptr(self.dx0), self.dx_ld, 0, None, 0, 1, 0, s)
+
+    def _layer_reg(self, l):
+        """(l2, element count, l1 flag, sum-of-squares word) of the regulariser on hidden weight
+        matrix l: wdl L2 (wdl.py:272-275), dnn L1 (dnn.py:88-90); the bias row excluded."""
+        sp = self.spec
+        reg = sp.hidden_reg
+        if not reg:
+            return 0.0, 0, 0, None
+        return sp.l2, ([self.D0] + sp.hidden)[l] * self.out_ld[l], 1 if reg == "l1" else 0, ptr(self.opt[8:])
+
+    def _tower_adam(self, l, grad, nsplit, s):
+        """TF1 Adam on layer l from `grad`, `nsplit` slabs one layer's stride apart."""
+        stride = self.in_ld[l] * self.out_ld[l]
+        l2, l2n, l1, reg_sum = self._layer_reg(l)
+        if self.s3 or self.bf:   # the update writes the GEMM operand copies of W and W^T itself
+            self._c("adam_dense_l%d" % l, "dl_adam_dense_split3" if self.s3 else "dl_adam_dense_bf16",
+                    ptr(self.W[l]), ptr(self.Wm[l]), ptr(self.Wv[l]), ptr(grad), nsplit, stride, self.in_ld[l],
+                    self.out_ld[l], l2, l2n, l1, ptr(self.opt), reg_sum,
+                    ptr(self.Wp[l] if self.s3 else self.Wb[l]), ptr(self.WTp[l] if self.s3 else self.WbT[l]), s)
+            return
+        self._c("adam_dense_l%d" % l, "dl_adam_dense_reg", ptr(self.W[l]), ptr(self.Wm[l]), ptr(self.Wv[l]),
+                ptr(grad), nsplit, stride, stride, l2, l2n, l1, ptr(self.opt), None, reg_sum, s)
+        self._refresh_wb(l, s)   # (launches nothing for an f32 tower)
 
     def _adam_fused(self):
         """The tower's dense Adams as one launch (dl_adam_dense_layers) after the backward's GEMMs

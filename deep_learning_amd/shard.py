@@ -171,6 +171,8 @@ class ShardedCTREngine(CTREngine):
         if sample_weight or spec.pos_weight != 1.0:
             raise ValueError("sample_weight / pos_weight: not supported by ShardedCTREngine (the loss normaliser, "
                              "the batch's nonzero-weight count, would need an all-reduce across the ranks)")
+        # (the tower's launches are the engine's own, dropout and cross forms included; what these
+        # options still lack here is named in each message)
         if spec.dropout:
             raise ValueError("dropout_keep_deep: not supported by ShardedCTREngine (the mask is indexed by the "
                              "local row number; a sharded batch needs global rows)")
@@ -620,45 +622,16 @@ class ShardedCTREngine(CTREngine):
                  ptr(self.rows_u1[o:]) if sp.fm else None, s)
 
     def _forward_local(self, B, s, train):
-        """Step 5a: the forward on this rank's batch from the exchanged rows."""
+        """Step 5a: the forward on this rank's batch from the exchanged rows; the tower is the
+        engine's (_tower_fwd, _tower_dx, _tower_dw, _tower_adam: one set of launches for both)."""
         sp = self.spec
         L = self.layout
         L.batch = B
         self._c("embed_fwd", "dl_embed_fwd_indexed", C_ref(L), ptr(self.rows_u), ptr(self.rows_u1) if sp.fm else None,
                 ptr(self.inv), self.rep, ptr(self.in_cont), ptr(self.in_vec),
                 ptr(self.x0b if self.x0_direct else self.x0), ptr(self.fm_out), ptr(self.fm_sum), s)
-        if self.bf and not self.x0_direct:
-            self._c("cast_x0", "dl_cast_bf16", ptr(self.x0), B, self.in_ld[0], self.in_ld[0], ptr(self.x0b),
-                    self.in_ld[0], s)
-        self._tower_fwd(B, s)
+        self._tower_fwd(B, s, train)
         self._head(B, s, train)
-
-    def _tower_fwd(self, B, s):
-        """Deep tower forward from x0 (f32 / three-plane split on bf16 MFMA / bf16 tower)."""
-        sp = self.spec
-        nl = len(sp.hidden)
-        if self.bf:
-            xb = self.x0b
-            for l, hdim in enumerate(sp.hidden):
-                last = l == nl - 1
-                out = self.h[l] if last else self.hb[l]
-                self._c("gemm_fwd_l%d" % l, "dl_gemm_bf16", 0, 1, B, hdim, self.in_ld[l], ptr(xb), self.in_ld[l],
-                        ptr(self.WbT[l]), self.in_ld[l], ptr(out), self.h_ld[l], 0 if last else 1, 1, None, 0, 1,
-                        0, s)
-                if not last:
-                    xb = self.hb[l]
-            return
-        x = self.x0
-        for l, hdim in enumerate(sp.hidden):
-            if self.s3:
-                bits = (ptr(self.hbits[l]), self.hbits_ld[l]) if l < len(self.hbits) else (None, 0)
-                self._c("gemm_fwd_l%d" % l, "dl_gemm_s3_nt_bits", B, hdim, self.in_ld[l], ptr(x), self.in_ld[l],
-                        ptr(self.WTp[l]), self.in_ld[l], self.in_ld[l] * self.out_ld[l], ptr(self.h[l]),
-                        self.h_ld[l], 1, None, 0, *bits, s)
-            else:
-                self._c("gemm_fwd_l%d" % l, "dl_gemm_f32", 0, 0, B, hdim, self.in_ld[l], ptr(x), self.in_ld[l],
-                        ptr(self.W[l]), self.out_ld[l], ptr(self.h[l]), self.h_ld[l], 1, None, 0, 1, 0, s)
-            x = self.h[l]
 
     def _head(self, B, s, train=True):
         """Output layer + loss: the FM / deep_res head, or the wdl cross logit on the local
@@ -682,46 +655,10 @@ class ShardedCTREngine(CTREngine):
     def _input_grads(self, B, s):
         """Step 5b: the input-gradient chain, top layer down to dx0, then every unique row's
         gradient into its slot (dl_embed_bwd_sorted with the route's slots)."""
-        sp = self.spec
         L = self.layout
-        nl = len(sp.hidden)
-        if self.bf and not self.wdl:
-            self._c("cast_dh", "dl_cast_bf16", ptr(self.dh[-1]), B, self.h_ld[-1], self.h_ld[-1], ptr(self.dhb[-1]),
-                    self.h_ld[-1], s)
-        for l in reversed(range(nl)):
-            if self.bf:
-                if l > 0:   # dX = dY . W^T, ReluGrad by the bf16 activations, bf16 out
-                    self._c("gemm_dx_l%d" % l, "dl_gemm_bf16", 0, 1, B, sp.hidden[l - 1], self.out_ld[l],
-                            ptr(self.dhb[l]), self.h_ld[l], ptr(self.Wb[l]), self.out_ld[l], ptr(self.dhb[l - 1]),
-                            self.h_ld[l - 1], 1, 2, ptr(self.hb[l - 1]), self.h_ld[l - 1], 1, 0, s)
-                else:       # dx0 stays fp32 for the embedding backward
-                    self._c("gemm_dx_l0", "dl_gemm_bf16", 0, 1, B, self.dx_cols, self.out_ld[0], ptr(self.dhb[0]),
-                            self.h_ld[0], ptr(self.Wb[0]), self.out_ld[0], ptr(self.dx0), self.dx_ld, 0, 0, None, 0,
-                            1, 0, s)
-                continue
-            if self.s3:
-                i, o = self.in_ld[l], self.out_ld[l]
-                if l > 0 and self.relu_bits:   # ReluGrad from the forward's sign bitmask
-                    self._c("gemm_dx_l%d" % l, "dl_gemm_s3_nt_bits", B, sp.hidden[l - 1], o, ptr(self.dh[l]),
-                            self.h_ld[l], ptr(self.Wp[l]), o, i * o, ptr(self.dh[l - 1]), self.h_ld[l - 1], 3,
-                            None, 0, ptr(self.hbits[l - 1]), self.hbits_ld[l - 1], s)
-                elif l > 0:
-                    self._c("gemm_dx_l%d" % l, "dl_gemm_s3_nt", B, sp.hidden[l - 1], o, ptr(self.dh[l]),
-                            self.h_ld[l], ptr(self.Wp[l]), o, i * o, ptr(self.dh[l - 1]), self.h_ld[l - 1], 2,
-                            ptr(self.h[l - 1]), self.h_ld[l - 1], s)
-                else:
-                    self._c("gemm_dx_l0", "dl_gemm_s3_nt", B, self.dx_cols, o, ptr(self.dh[0]), self.h_ld[0],
-                            ptr(self.Wp[0]), o, i * o, ptr(self.dx0), self.dx_ld, 0, None, 0, s)
-                continue
-            self._c("transpose_l%d" % l, "dl_transpose_f32", ptr(self.W[l]), self.in_ld[l], self.out_ld[l],
-                    self.out_ld[l], ptr(self.Wt), self.in_ld[l], s)
-            if l > 0:
-                self._c("gemm_dx_l%d" % l, "dl_gemm_f32", 0, 0, B, sp.hidden[l - 1], self.out_ld[l], ptr(self.dh[l]),
-                        self.h_ld[l], ptr(self.Wt), self.in_ld[l], ptr(self.dh[l - 1]), self.h_ld[l - 1], 2,
-                        ptr(self.h[l - 1]), self.h_ld[l - 1], 1, 0, s)
-            else:
-                self._c("gemm_dx_l0", "dl_gemm_f32", 0, 0, B, self.dx_cols, self.out_ld[0], ptr(self.dh[0]),
-                        self.h_ld[0], ptr(self.Wt), self.in_ld[0], ptr(self.dx0), self.dx_ld, 0, None, 0, 1, 0, s)
+        self._cast_dh(B, s)
+        for l in reversed(range(len(self.spec.hidden))):
+            self._tower_dx(l, B, s)
         self._c("embed_bwd", "dl_embed_bwd_sorted", C_ref(L), None, ptr(self.rows_u[self.rep:]), ptr(self.idx_uniq),
                 ptr(self.idx_off), ptr(self.idx_n), ptr(self.idx_refs), self.world, B * self.n_slot, ptr(self.dz),
                 ptr(self.w_head), ptr(self.fm_sum), ptr(self.dx0), ptr(self.g_all), ptr(self.g1_all), None, 1,
@@ -735,25 +672,11 @@ class ShardedCTREngine(CTREngine):
         nl = len(sp.hidden)
         dws = self._dw_splits(B, fixed="DLAMD_DW_SPLITS" in os.environ)
         for l in reversed(range(nl)):
-            splits = dws[l]
-            xin = self.x0 if l == 0 else self.h[l - 1]
-            hdim = sp.hidden[l]
-            stride = self.in_ld[l] * self.out_ld[l]
-            if self.bf:
-                xl = self.x0b if l == 0 else self.hb[l - 1]
-                self._c("gemm_dw_l%d" % l, "dl_gemm_bf16", 1, 0, self.in_ld[l], hdim, B, ptr(xl), self.in_ld[l],
-                        ptr(self.dhb[l]), self.h_ld[l], ptr(self.w_slab), self.out_ld[l], 0, 3, None, 0, splits,
-                        stride, s)
-            elif self.s3:
-                self._c("gemm_dw_l%d" % l, "dl_gemm_s3_tn", self.in_ld[l], hdim, B, ptr(xin), self.in_ld[l],
-                        ptr(self.dh[l]), self.h_ld[l], ptr(self.w_slab), self.out_ld[l], splits, stride, s)
-            else:
-                self._c("gemm_dw_l%d" % l, "dl_gemm_f32", 1, 0, self.in_ld[l], hdim, B, ptr(xin), self.in_ld[l],
-                        ptr(self.dh[l]), self.h_ld[l], ptr(self.w_slab), self.out_ld[l], 3, None, 0, splits, stride,
-                        s)
+            self._tower_dw(l, B, dws[l], self.w_slab, s)
+            _, off, stride = self.seg[l]
             self._c("slab_sum_l%d" % l, "dl_slab_sum", ptr(self.w_slab),
-                    _num_splits(B, splits, 64 if (self.s3 or self.bf) else 16), stride, stride,
-                    ptr(self.flat[self.seg[l][1]:]), s)
+                    _num_splits(B, dws[l], 64 if (self.s3 or self.bf) else 16), stride, stride,
+                    ptr(self.flat[off:]), s)
         hoff = self.seg[nl][1]
         self._c("slab_sum_head", "dl_slab_sum", ptr(self.head_slab), call_int(self.head_grid, B), self.head_w,
                 self.head_w, ptr(self.flat[hoff:]), s)
@@ -783,20 +706,8 @@ class ShardedCTREngine(CTREngine):
         E = sp.E
         nl = len(sp.hidden)
         hoff = self.seg[nl][1]
-        reg = sp.hidden_reg   # wdl: L2 on every hidden weight matrix (wdl.py:272-275), bias row excluded
         for l in range(nl):
-            off, sz = self.seg[l][1], self.seg[l][2]
-            l2, l2n = (sp.l2, ([self.D0] + sp.hidden)[l] * self.out_ld[l]) if reg else (0.0, 0)
-            if self.s3 or self.bf:
-                self._c("adam_dense_l%d" % l, "dl_adam_dense_split3" if self.s3 else "dl_adam_dense_bf16",
-                        ptr(self.W[l]), ptr(self.Wm[l]), ptr(self.Wv[l]), ptr(self.flat[off:]), 1, sz, self.in_ld[l],
-                        self.out_ld[l], l2, l2n, 1 if reg == "l1" else 0, ptr(self.opt),
-                        ptr(self.opt[8:]) if reg else None, ptr(self.Wp[l] if self.s3 else self.Wb[l]),
-                        ptr(self.WTp[l] if self.s3 else self.WbT[l]), s)
-            else:
-                self._c("adam_dense_l%d" % l, "dl_adam_dense_reg", ptr(self.W[l]), ptr(self.Wm[l]), ptr(self.Wv[l]),
-                        ptr(self.flat[off:]), 1, sz, sz, l2, l2n, 1 if reg == "l1" else 0, ptr(self.opt), None,
-                        ptr(self.opt[8:]) if reg else None, s)
+            self._tower_adam(l, self.flat[self.seg[l][1]:], 1, s)
         if self.wdl:
             H = sp.hidden[-1]
             self._c("adam_bias", "dl_adam_dense", ptr(self.wb), ptr(self.wbm), ptr(self.wbv), ptr(self.flat[hoff + H:]),

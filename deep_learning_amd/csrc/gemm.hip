@@ -19,8 +19,15 @@
 // 16-lane k-rows of an MFMA operand read land in disjoint banks.
 // Block -> tile mapping is XCD-aware: tiles that share the A rows are dealt to
 // blocks b, b+8, ... which the dispatcher places on one XCD (speed only).
+//
+// Kernels in this file:
+//   gemm_f32_kernel        every dl_gemm_f32 product (tile shapes picked by dispatch_bn_f32)
+//   gemm_bf16_dw3_kernel   bf16 weight gradients (ta = 1, tb = 0, split slabs), LDS-DMA ring
+//   gemm_bf16_dw_kernel    the same with two buffers: the batch sizes the ring kernel declines
+//   gemm_bf16_nt_kernel    bf16 forward / dX (ta = 0, tb = 1), register or LDS epilogue
+//   gemm_bf16_kernel       every other dl_gemm_bf16 product (any ta / tb, alignment, size)
+//   cast_bf16_kernel, transpose_bf16_kernel, transpose_kernel
 #include "common.h"
-#include <cstdlib>
 
 namespace dl {
 
@@ -28,12 +35,7 @@ typedef float floatx4 __attribute__((ext_vector_type(4)));
 typedef unsigned int dl_u32x4_t __attribute__((__vector_size__(4 * sizeof(unsigned int))));
 typedef unsigned int dl_u32x2_t __attribute__((__vector_size__(2 * sizeof(unsigned int))));
 
-#ifndef DL_GEMM_BK
-#define DL_GEMM_BK 16   // k-slab per LDS stage of the f32 GEMM
-#endif
-#ifndef DL_GEMM_GLDS
-#define DL_GEMM_GLDS 0  // LDS-DMA for the k-contiguous A tile (correct, measured neutral: DESIGN.md §4)
-#endif
+constexpr int kGemmBK = 16;   // k-slab per LDS stage of the f32 GEMM
 
 struct GemmParams {
   const void* A;
@@ -71,7 +73,7 @@ __device__ __forceinline__ int xcd_tile(int bid, int T) {
 // left a 17 % tail).
 template <int BM, int BN>
 struct GemmOcc {
-  static constexpr int waves = (BM == 128 && BN <= 80 && DL_GEMM_BK == 16) ? 5 : (BM > 128 ? 3 : 2);
+  static constexpr int waves = (BM == 128 && BN <= 80) ? 5 : (BM > 128 ? 3 : 2);
 };
 
 // FAST: M % BM == 0, N % BN == 0 and every split's k range whole BK slabs (the tower's
@@ -91,16 +93,10 @@ void gemm_f32_kernel(GemmParams p) {
   constexpr int FM = WTM / 16, FN = WTN / 16;
   constexpr int QA = (BM * BK / 4 + NT - 1) / NT;  // float4 staged per thread
   constexpr int QB = (BN * BK / 4 + NT - 1) / NT;
-  static_assert(WM * WN == 4 || (WM * WN == 5 && !(DL_GEMM_GLDS && !TA)), "4 waves (or 5 without LDS-DMA)");
+  static_assert(WM * WN == 4 || WM * WN == 5, "4 or 5 waves");
   static_assert(WTM % 16 == 0 && WTN % 16 == 0 && BK % 16 == 0, "tile shape");
 
-  // GLDS: the k-contiguous A tile is filled by LDS-DMA (global_load_lds_dwordx4), which
-  // writes lane-linear 1 KB pieces: the image is unpadded [row][16] and conflict-free
-  // b128 reads come from an XOR swizzle of the 16-B chunks, applied on the SOURCE
-  // address: slot(row, chunk) = 4*row + (chunk ^ ((row >> 1) & 3)).
-  constexpr bool GLDS = DL_GEMM_GLDS && AKC && BK == 16;
-  constexpr int A_LD_EFF = GLDS ? BK : A_LD;
-  __shared__ __attribute__((aligned(16))) float As[2][A_ROWS][A_LD_EFF];
+  __shared__ __attribute__((aligned(16))) float As[2][A_ROWS][A_LD];
   __shared__ __attribute__((aligned(16))) float Bs[2][B_ROWS][B_LD];
 
   const float* __restrict__ A = reinterpret_cast<const float*>(p.A);
@@ -147,26 +143,12 @@ void gemm_f32_kernel(GemmParams p) {
       else b_off[u] = 4u * (unsigned)((qi / (BK / 4)) * p.ldb + 4 * (qi % (BK / 4)));
     }
   }
-  auto glds_a = [&](int k0, int buf) {
-    // 8 pieces of 16 rows for BM = 128: wave w issues pieces w, w + 4, ...
-#pragma unroll
-    for (int g = wid; g < BM / 16; g += 4) {
-      const int row = g * 16 + (lane >> 2);
-      const int chunk = (lane & 3) ^ ((row >> 1) & 3);
-      int gi = i0 + row;
-      gi = gi < p.M ? gi : p.M - 1;                    // rows past M: any valid row (outputs dropped)
-      int gr = k0 + 4 * chunk;
-      gr = gr < kend ? gr : kend - 4;                  // k past kend: B is zero there
-      const float* src = A + (long long)gi * p.lda + gr;
-      __builtin_amdgcn_global_load_lds(src, (__attribute__((address_space(3))) void*)&As[buf][g * 16][0], 16, 0, 0);
-    }
-  };
   auto load_tile = [&](int k0) {
     if (FAST) {
       const unsigned ks = (unsigned)((k0 - kbeg) / BK);
       const int sa = (int)(ks * a_step), sb = (int)(ks * b_step);
 #pragma unroll
-      for (int u = 0; u < (GLDS ? 0 : QA); ++u) {
+      for (int u = 0; u < QA; ++u) {
         const auto v = __builtin_amdgcn_raw_buffer_load_b128(a_rsrc, (int)a_off[u], sa, 0);
         ra[u] = make_float4(__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]), __uint_as_float(v[3]));
       }
@@ -177,7 +159,7 @@ void gemm_f32_kernel(GemmParams p) {
       }
     } else {
 #pragma unroll
-    for (int u = 0; u < (GLDS ? 0 : QA); ++u) {
+    for (int u = 0; u < QA; ++u) {
       const int qi = tid + u * NT;
       float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
       if (qi < BM * BK / 4) {
@@ -214,7 +196,7 @@ void gemm_f32_kernel(GemmParams p) {
   };
   auto store_tile = [&](int buf) {
 #pragma unroll
-    for (int u = 0; u < (GLDS ? 0 : QA); ++u) {
+    for (int u = 0; u < QA; ++u) {
       const int qi = tid + u * NT;
       if (qi < BM * BK / 4) {
         if (TA) {
@@ -242,7 +224,6 @@ void gemm_f32_kernel(GemmParams p) {
   };
 
   if (nk > 0) {
-    if (GLDS) glds_a(kbeg, 0);
     load_tile(kbeg);
     store_tile(0);
     __syncthreads();
@@ -254,19 +235,14 @@ void gemm_f32_kernel(GemmParams p) {
   const bool live = FAST || (i0 + wm * WTM < p.M && j0 + wn * WTN < p.N);
   for (int kt = 0; kt < nk; ++kt) {
     const int cur = kt & 1;
-    if (GLDS && kt + 1 < nk) glds_a(kbeg + (kt + 1) * BK, cur ^ 1);
     if (kt + 1 < nk) load_tile(kbeg + (kt + 1) * BK);
 #pragma unroll
     for (int s16 = 0; s16 < (live ? BK / 16 : 0); ++s16) {
       float4 a4[AKC ? FM : 1], b4[BKC ? FN : 1];
       if (AKC) {
 #pragma unroll
-        for (int a = 0; a < FM; ++a) {
-          if (GLDS)
-            a4[a] = *reinterpret_cast<const float4*>(&As[cur][wm * WTM + a * 16 + cl][4 * (kr ^ ((cl >> 1) & 3))]);
-          else
-            a4[a] = *reinterpret_cast<const float4*>(&As[cur][AKC ? wm * WTM + a * 16 + cl : 0][s16 * 16 + 4 * kr]);
-        }
+        for (int a = 0; a < FM; ++a)
+          a4[a] = *reinterpret_cast<const float4*>(&As[cur][AKC ? wm * WTM + a * 16 + cl : 0][s16 * 16 + 4 * kr]);
       }
       if (BKC) {
 #pragma unroll
@@ -421,314 +397,15 @@ __global__ __launch_bounds__(256) void cast_bf16_kernel(const float* __restrict_
   }
 }
 
-// bf16 GEMM with both operands k-contiguous in HBM (A [i][k], B given as [j][k], i.e.
-// ta = 0, tb = 1): the tower's forward (B = W^T copy), dX (B = W) and dW (A = X^T, B = dY^T
-// copies) are all put in this form by the engine, so every LDS image is a straight b128
-// copy and every MFMA fragment one ds_read_b128: lane (cl, kq) holds A[i = cl][k = 8kq..8kq+7]
-// and B[k = 8kq..8kq+7][j = cl] of v_mfma_f32_16x16x32_bf16.  BK = 64 (two MFMA k-steps),
-// LDS rows padded to 80 bf16 = 40 words (conflict-free for the b128 lane groups).
-template <int BM, int BN, int WM, int WN, int EPI, bool CBF16>
-__global__ __launch_bounds__(256) void gemm_bf16_kc_kernel(GemmParams p) {
-  constexpr int BK = 64, SK = BK + 16;
-  constexpr int WTM = BM / WM, WTN = BN / WN;
-  constexpr int FM = WTM / 16, FN = WTN / 16;
-  constexpr int QA = (BM * BK / 8 + 255) / 256, QB = (BN * BK / 8 + 255) / 256;   // uint4 per thread
-  static_assert(WM * WN == 4 && WTM % 16 == 0 && WTN % 16 == 0, "tile");
-  __shared__ __attribute__((aligned(16))) unsigned short As[2][BM][SK];
-  __shared__ __attribute__((aligned(16))) unsigned short Bs[2][BN][SK];
-  const unsigned short* __restrict__ A = reinterpret_cast<const unsigned short*>(p.A);
-  const unsigned short* __restrict__ Bm = reinterpret_cast<const unsigned short*>(p.B);
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const int wm = wid / WN, wn = wid % WN;
-  const int ntm = (p.M + BM - 1) / BM, ntn = (p.N + BN - 1) / BN;
-  const int t = xcd_tile(blockIdx.x, ntm * ntn);
-  const int i0 = (t / ntn) * BM, j0 = (t % ntn) * BN;
-  const int kbeg = blockIdx.z * p.k_per_split;
-  const int kend = min(p.K, kbeg + p.k_per_split);
-  const int nk = (kend - kbeg + BK - 1) / BK;
-  floatx4 acc[FM][FN];
-#pragma unroll
-  for (int a = 0; a < FM; ++a)
-#pragma unroll
-    for (int b = 0; b < FN; ++b) acc[a][b] = floatx4{0.f, 0.f, 0.f, 0.f};
-  uint4 ra[QA], rb[QB];
-  const uint4 z4 = make_uint4(0u, 0u, 0u, 0u);
-  auto load_tile = [&](int k0) {
-#pragma unroll
-    for (int u = 0; u < QA; ++u) {
-      const int q = tid + u * 256, i = q / (BK / 8), k8 = q % (BK / 8);
-      const int gi = i0 + i, gk = k0 + 8 * k8;
-      ra[u] = (q < BM * BK / 8 && gi < p.M && gk < kend)
-                  ? *reinterpret_cast<const uint4*>(A + (long long)gi * p.lda + gk) : z4;
-    }
-#pragma unroll
-    for (int u = 0; u < QB; ++u) {
-      const int q = tid + u * 256, j = q / (BK / 8), k8 = q % (BK / 8);
-      const int gj = j0 + j, gk = k0 + 8 * k8;
-      rb[u] = (q < BN * BK / 8 && gj < p.N && gk < kend)
-                  ? *reinterpret_cast<const uint4*>(Bm + (long long)gj * p.ldb + gk) : z4;
-    }
-  };
-  auto store_tile = [&](int buf) {
-#pragma unroll
-    for (int u = 0; u < QA; ++u) {
-      const int q = tid + u * 256;
-      if (q < BM * BK / 8) *reinterpret_cast<uint4*>(&As[buf][q / (BK / 8)][8 * (q % (BK / 8))]) = ra[u];
-    }
-#pragma unroll
-    for (int u = 0; u < QB; ++u) {
-      const int q = tid + u * 256;
-      if (q < BN * BK / 8) *reinterpret_cast<uint4*>(&Bs[buf][q / (BK / 8)][8 * (q % (BK / 8))]) = rb[u];
-    }
-  };
-  if (nk > 0) {
-    load_tile(kbeg);
-    store_tile(0);
-    __syncthreads();
-  }
-  const int cl = lane & 15, kq = lane >> 4;
-  for (int kt = 0; kt < nk; ++kt) {
-    const int cur = kt & 1;
-    if (kt + 1 < nk) load_tile(kbeg + (kt + 1) * BK);
-#pragma unroll
-    for (int s = 0; s < BK / 32; ++s) {
-      shortx8 av[FM], bv[FN];
-#pragma unroll
-      for (int a = 0; a < FM; ++a)
-        av[a] = *reinterpret_cast<const shortx8*>(&As[cur][wm * WTM + a * 16 + cl][32 * s + 8 * kq]);
-#pragma unroll
-      for (int b = 0; b < FN; ++b)
-        bv[b] = *reinterpret_cast<const shortx8*>(&Bs[cur][wn * WTN + b * 16 + cl][32 * s + 8 * kq]);
-#pragma unroll
-      for (int a = 0; a < FM; ++a)
-#pragma unroll
-        for (int b = 0; b < FN; ++b)
-          acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[a], bv[b], acc[a][b], 0, 0, 0);
-    }
-    if (kt + 1 < nk) store_tile(cur ^ 1);
-    __syncthreads();
-  }
-  const int kr = lane >> 4;
-  const long long zoff = (EPI == EPI_SPLIT) ? (long long)blockIdx.z * p.c_split_stride : 0;
-#pragma unroll
-  for (int a = 0; a < FM; ++a)
-#pragma unroll
-    for (int b = 0; b < FN; ++b) {
-      const int col = j0 + wn * WTN + b * 16 + cl;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int row = i0 + wm * WTM + a * 16 + kr * 4 + j;
-        if (row < p.M && col < p.N) {
-          float v = acc[a][b][j];
-          if (EPI == EPI_RELU) v = fmaxf(v, 0.f);
-          if (EPI == EPI_MASK) {
-            const unsigned short* mk = reinterpret_cast<const unsigned short*>(p.mask);
-            v = bf2f(mk[(long long)row * p.ldm + col]) > 0.f ? v : 0.f;
-          }
-          const long long o = zoff + (long long)row * p.ldc + col;
-          if (CBF16) reinterpret_cast<unsigned short*>(p.C)[o] = f2bf(v);
-          else reinterpret_cast<float*>(p.C)[o] = v;
-        }
-      }
-    }
-}
-
-// Tall-skinny bf16 product with the B tile resident in LDS (the C5 tower's forward and dX:
-// M = batch rows, N <= 416, K <= 448, both operands k-contiguous).  A block owns 256 rows x
-// 80 columns: its whole B slab (80 x K bf16, <= 72 KB) is loaded into LDS once, and each
-// of its 8 waves streams its own 32 rows of A straight into MFMA fragments (16 B per lane
-// per 32-deep k-chunk; A is read once per column tile, the column tiles of a row tile
-// placed on one XCD) with a KC-chunk fully unrolled loop whose loads run DEPTH chunks
-// ahead.  The generic kc kernel re-staged both operands every 64-deep step and waited a
-// full memory round trip per step (7 steps per tile): 139 us for the 65536 x 400 x 432
-// forward; this one is bound by streaming A.
-template <int KC, int EPI, bool CBF16>
-__global__ __launch_bounds__(512) void gemm_bf16_bres_kernel(GemmParams p) {
-  constexpr int BM = 256, BN = 80, NF = BN / 16, DEPTH = 3;
-  constexpr int KP = KC * 32 + 8;                 // LDS row pitch (bf16): +16 B keeps b128 reads conflict-free
-  extern __shared__ __attribute__((aligned(16))) unsigned short Bs[];   // [BN][KP]
-  const unsigned short* __restrict__ A = reinterpret_cast<const unsigned short*>(p.A);
-  const unsigned short* __restrict__ Bm = reinterpret_cast<const unsigned short*>(p.B);
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const int ntm = (p.M + BM - 1) / BM, ntn = (p.N + BN - 1) / BN;
-  const int t = xcd_tile(blockIdx.x, ntm * ntn);
-  const int i0 = (t / ntn) * BM, j0 = (t % ntn) * BN;
-  const int cl = lane & 15, kq = lane >> 4;
-  const uint4 z4 = make_uint4(0u, 0u, 0u, 0u);
-  // A fragments of this wave: rows r0 + cl and r0 + 16 + cl, k = 32c + 8kq .. +7
-  const int r0 = i0 + wid * 32;
-  // A through a buffer descriptor (the host checks M * lda * 2 < 2^31): a piece past M or K
-  // gets an offset past the range and reads as zeros — no select on a loaded value, which
-  // made hipcc wait for each load where it was issued
-  const auto a_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.A, (short)0, p.M * p.lda * 2, 0x00020000);
-  const uint32_t o0 = 2u * (uint32_t)(min(r0 + cl, p.M - 1) * p.lda + 8 * kq);
-  const uint32_t o1 = 2u * (uint32_t)(min(r0 + 16 + cl, p.M - 1) * p.lda + 8 * kq);
-  const bool ok0 = r0 + cl < p.M, ok1 = r0 + 16 + cl < p.M;
-  auto lda_ = [&](int c, uint4 (&r)[2]) {
-    const bool kin = 32 * c + 8 * kq < p.K;
-    r[0] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(a_rsrc, (int)((ok0 & kin) ? o0 + 64u * c : 0x80000000u), 0, 0));
-    r[1] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(a_rsrc, (int)((ok1 & kin) ? o1 + 64u * c : 0x80000000u), 0, 0));
-  };
-  uint4 ra[KC][2];
-#pragma unroll
-  for (int c = 0; c < DEPTH && c < KC; ++c) lda_(c, ra[c]);
-  // B slab -> LDS: row j (column j0 + j of the product), k contiguous, zero past N and K
-  for (int q = tid; q < BN * KC * 4; q += 512) {
-    const int j = q / (KC * 4), k8 = q % (KC * 4);
-    const int gj = j0 + j, gk = 8 * k8;
-    const uint4 v = (gj < p.N && gk < p.K) ? *reinterpret_cast<const uint4*>(Bm + (long long)gj * p.ldb + gk) : z4;
-    *reinterpret_cast<uint4*>(&Bs[j * KP + gk]) = v;
-  }
-  __syncthreads();
-  floatx4 acc[2][NF];
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int f = 0; f < NF; ++f) acc[a][f] = floatx4{0.f, 0.f, 0.f, 0.f};
-  // every fragment (the slab is zero past N): no per-fragment branch to stop the scheduler
-  // from overlapping the next fragment's read with this one's MFMAs
-#pragma unroll
-  for (int c = 0; c < KC; ++c) {
-    if (c + DEPTH < KC) lda_(c + DEPTH, ra[c + DEPTH]);
-    const shortx8 av0 = __builtin_bit_cast(shortx8, ra[c][0]);
-    const shortx8 av1 = __builtin_bit_cast(shortx8, ra[c][1]);
-#pragma unroll
-    for (int f = 0; f < NF; ++f) {
-      const shortx8 bv = *reinterpret_cast<const shortx8*>(&Bs[(16 * f + cl) * KP + 32 * c + 8 * kq]);
-      acc[0][f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av0, bv, acc[0][f], 0, 0, 0);
-      acc[1][f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av1, bv, acc[1][f], 0, 0, 0);
-    }
-  }
-  // Epilogue through LDS (the B slab is dead now): each wave writes its 32 x 80 tile row-major
-  // (element stores from the MFMA layout), then every lane moves whole 16-B row pieces, so the
-  // output (and the ReluGrad mask) go to HBM as full row segments instead of 2/4-byte
-  // scatters.  f32 output goes in two 16-row halves (32 x 80 x 4 B would not fit beside the
-  // other waves' tiles).
-  __syncthreads();
-  constexpr int ES = CBF16 ? 2 : 4;                 // output element bytes
-  constexpr int HR = CBF16 ? 32 : 16;               // rows per pass
-  constexpr int TP = BN + (CBF16 ? 8 : 4);          // tile pitch (elements): rows start 16-B aligned
-  constexpr int EPP = 16 / ES;                      // elements per 16-B piece
-  constexpr int VPR = BN / EPP;                     // pieces per row (10 or 20)
-  unsigned char* tile = reinterpret_cast<unsigned char*>(Bs) + (size_t)wid * HR * TP * ES;
-  constexpr int NIT = (HR * VPR + 63) / 64;         // pieces per lane per pass
-#pragma unroll
-  for (int h = 0; h < 32 / HR; ++h) {
-    // the ReluGrad mask's pieces of this pass, loaded before the tile's LDS writes: all in
-    // flight together instead of one dependent round trip per piece
-    uint4 mkr[EPI == EPI_MASK ? NIT : 1];
-    if (EPI == EPI_MASK) {
-#pragma unroll
-      for (int it = 0; it < NIT; ++it) {
-        const int q = min(lane + 64 * it, HR * VPR - 1);
-        const int rl = q / VPR, pc = q % VPR;
-        const int row = min(r0 + HR * h + rl, p.M - 1), col = max(0, min(j0 + pc * EPP, p.N - EPP));
-        const unsigned short* mk = reinterpret_cast<const unsigned short*>(p.mask) + (long long)row * p.ldm + col;
-        if (CBF16) {
-          mkr[it] = *reinterpret_cast<const uint4*>(mk);
-        } else {
-          const uint2 m2 = *reinterpret_cast<const uint2*>(mk);
-          mkr[it] = make_uint4(m2.x, m2.y, 0u, 0u);
-        }
-      }
-    }
-#pragma unroll
-    for (int a = 0; a < 2; ++a) {
-      if (16 * a < HR * h || 16 * a >= HR * (h + 1)) continue;
-#pragma unroll
-      for (int f = 0; f < NF; ++f)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const int rl = 16 * a + 4 * kq + j - HR * h, cc = 16 * f + cl;
-          float v = acc[a][f][j];
-          if (EPI == EPI_RELU) v = fmaxf(v, 0.f);
-          if (CBF16) reinterpret_cast<unsigned short*>(tile)[rl * TP + cc] = f2bf(v);
-          else reinterpret_cast<float*>(tile)[rl * TP + cc] = v;
-        }
-    }
-    __builtin_amdgcn_s_waitcnt(0xc07f);             // lgkmcnt(0): this wave's tile writes landed
-    __builtin_amdgcn_wave_barrier();
-#pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-      const int q = lane + 64 * it;
-      const int rl = q / VPR, pc = q % VPR;
-      const int row = r0 + HR * h + rl, col = j0 + pc * EPP;
-      if (q >= HR * VPR || row >= p.M || col >= p.N) continue;
-      uint4 v = *reinterpret_cast<const uint4*>(tile + ((size_t)rl * TP * ES + pc * 16));
-      const int nv = min(EPP, p.N - col);           // elements of this piece inside N
-      if (EPI == EPI_MASK) {
-        const unsigned short* mk = reinterpret_cast<const unsigned short*>(p.mask) + (long long)row * p.ldm + col;
-        unsigned short mv[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        if (nv == EPP && (reinterpret_cast<uintptr_t>(mk) & (2 * EPP - 1)) == 0) {
-          const uint4 m4 = mkr[EPI == EPI_MASK ? it : 0];
-          memcpy(mv, &m4, CBF16 ? 16 : 8);
-        } else {
-          for (int e = 0; e < nv; ++e) mv[e] = mk[e];
-        }
-        if (CBF16) {
-          unsigned short x[8];
-          memcpy(x, &v, 16);
-          for (int e = 0; e < 8; ++e) x[e] = bf2f(mv[e]) > 0.f ? x[e] : (unsigned short)0;
-          memcpy(&v, x, 16);
-        } else {
-          float x[4];
-          memcpy(x, &v, 16);
-          for (int e = 0; e < 4; ++e) x[e] = bf2f(mv[e]) > 0.f ? x[e] : 0.f;
-          memcpy(&v, x, 16);
-        }
-      }
-      unsigned char* dst = reinterpret_cast<unsigned char*>(p.C) + ((long long)row * p.ldc + col) * ES;
-      if (nv == EPP && (reinterpret_cast<uintptr_t>(dst) & 15) == 0) {
-        *reinterpret_cast<uint4*>(dst) = v;
-      } else {
-        unsigned char src[16];
-        memcpy(src, &v, 16);
-        for (int e = 0; e < nv; ++e) {
-          if (CBF16) { unsigned short w; memcpy(&w, src + 2 * e, 2); reinterpret_cast<unsigned short*>(dst)[e] = w; }
-          else { float w; memcpy(&w, src + 4 * e, 4); reinterpret_cast<float*>(dst)[e] = w; }
-        }
-      }
-    }
-    __builtin_amdgcn_wave_barrier();
-  }
-}
-
-template <int KC>
-static void launch_bf16_bres_kc(const GemmParams& gp, int epi, bool cb, hipStream_t s) {
-  const int tiles = (int)(ceil_div(gp.M, 256) * ceil_div(gp.N, 80));
-  const size_t lds = (size_t)80 * (KC * 32 + 8) * sizeof(unsigned short);
-  const dim3 grid(tiles), block(512);
-#define DL_BRES(E_, C_) hipLaunchKernelGGL((gemm_bf16_bres_kernel<KC, E_, C_>), grid, block, lds, s, gp)
-  if (epi == EPI_STORE) {
-    if (cb) DL_BRES(EPI_STORE, true); else DL_BRES(EPI_STORE, false);
-  } else if (epi == EPI_RELU) {
-    if (cb) DL_BRES(EPI_RELU, true); else DL_BRES(EPI_RELU, false);
-  } else {
-    if (cb) DL_BRES(EPI_MASK, true); else DL_BRES(EPI_MASK, false);
-  }
-#undef DL_BRES
-}
-
-// true if the B-resident kernel takes the product (and launches it)
-static bool launch_bf16_bres(const GemmParams& gp, int epi, bool cb, hipStream_t s) {
-  if (epi == EPI_SPLIT || gp.K <= 0 || gp.K > 448 || gp.K % 8 || gp.lda % 8 || gp.ldb % 8 || gp.M < 256 ||
-      (long long)gp.M * gp.lda * 2 >= (1LL << 31))
-    return false;
-  const int kc = (gp.K + 31) / 32;
-  if (kc <= 13) launch_bf16_bres_kc<13>(gp, epi, cb, s);
-  else launch_bf16_bres_kc<14>(gp, epi, cb, s);
-  return true;
-}
-
 // ---------------------------------------------------------------------------
 // Tall-skinny bf16 product with the weights streamed through an LDS ring (the C5 tower's
 // forward and dX: M = batch rows, both operands k-contiguous bf16).  The structure of the
 // s3 NT kernel (gemm_s3.hip) on one plane: block 256 x 208 (8 waves x 32 rows x 13 column
 // fragments), A streamed from HBM straight into MFMA fragments (one 16-B load per lane and
 // row fragment per 32-deep chunk), each chunk's [208][32] weight image (conflict-free slot
-// swizzle) filled by LDS-DMA two chunks ahead into a ring of three.  Against the B-resident
-// kernel above (256 x 80 blocks: A fetched once per 80 columns, five times for N = 400) a
-// block covers 208 columns, so A is fetched twice; the weight chunks come from L2.
+// swizzle) filled by LDS-DMA two chunks ahead into a ring of three.  A block covers 208
+// columns, so for N = 400 A is fetched twice (80-column blocks would fetch it five times);
+// the weight chunks come from L2.
 constexpr int kBnBM = 256, kBnBN = 208, kBnNF = 13;
 constexpr int kBnPlane = kBnBN * 32;                         // bf16 elements of one chunk image (13,312 B)
 constexpr int kBnDma = kBnBN / 16;                           // DMA instructions per chunk (13)
@@ -736,26 +413,8 @@ constexpr int kBnDmaW = (kBnDma + 7) / 8;                    // per wave (2; the
 constexpr int kBnEP = kBnBN + 4;                             // epilogue tile pitch (floats)
 constexpr size_t kBnLds = 8 * 16 * kBnEP * sizeof(float);    // the epilogue tiles: 108,544 B
 static_assert(3 * kBnPlane * sizeof(unsigned short) <= kBnLds, "the ring fits in the epilogue's LDS");
-#ifndef DL_BN_PF
-#define DL_BN_PF 4   // weight fragments read this many fragments ahead of their MFMAs
-#endif
-// DL_BN_ASMA: where each step takes its A chunk.  hipcc counts only its own loads in vmcnt (not
-// the weight LDS-DMA, inline asm), and it hoisted the copy of the next step's A registers into
-// the current step, where that load is the youngest it knows of: a vmcnt(0) drain in the middle
-// of every chunk's MFMAs (the weights two chunks ahead included).  With the copy made by an asm
-// statement it stays at its step's start, after the barrier (also asm), where hipcc's wait for
-// the chunk's A is vmcnt(2): it lets the next chunk's A loads stay in flight.
-#ifndef DL_BN_ASMA
-#define DL_BN_ASMA 1
-#endif
-// DL_BN_WIDE: bf16 output stored as 16-B pieces (two fragments' lane rows exchanged by
-// v_permlane16_swap, so a lane holds 8 consecutive columns) instead of 8-B pieces
-#ifndef DL_BN_WIDE
-#define DL_BN_WIDE 1
-#endif
-#ifndef DL_BN_NW
-#define DL_BN_NW 8   // waves a block of the register-epilogue NT kernel (gemm_bf16_nt_kernel NWV)
-#endif
+constexpr int kBnPF = 4;   // weight fragments read this many fragments ahead of their MFMAs
+constexpr int kBnNW = 8;   // waves a block (32 rows each: kBnBM)
 typedef unsigned int bn_u32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bn_bf16x2 __attribute__((ext_vector_type(2)));
 typedef float bn_f32x2 __attribute__((ext_vector_type(2)));
@@ -774,14 +433,12 @@ __device__ __forceinline__ int bn_slot(int j, int kq) { return kq ^ ((j >> 2) & 
 // accumulator holds four consecutive columns of one output row, and the epilogue stores them
 // straight from registers (8 B of bf16 or 16 B of f32 per lane and fragment; the ReluGrad mask's
 // four bf16 read the same way) instead of transposing each wave's tile through LDS (gemm_s3.hip's
-// register epilogue).  Needs N, ldc, ldm multiples of 4 (the host picks it then).
-// NWV: waves a block (32 rows each; 8 = 256-row blocks, one a CU; 4 = 128-row blocks, three a
-// CU at 155 VGPRs — the register epilogue only, its LDS being the 40-KB ring).
-template <int EPI, bool CBF16, bool DIRECT = false, int NWV = 8>
-__global__ __launch_bounds__(64 * NWV) void gemm_bf16_nt_kernel(GemmParams p) {
+// register epilogue).  Needs N, ldc, ldm multiples of 4 (the host picks it then); any other
+// width (a hidden width or (S+M)*E that is no multiple of 4) takes the LDS epilogue.
+template <int EPI, bool CBF16, bool DIRECT>
+__global__ __launch_bounds__(64 * kBnNW) void gemm_bf16_nt_kernel(GemmParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned short lds[];   // [3 bufs][BN][32], then the epilogue
-  static_assert(NWV == 8 || DIRECT, "the LDS epilogue's tiles assume 8 waves");
-  constexpr int NW = NWV, BM = 32 * NWV, DMAW = (kBnDma + NWV - 1) / NWV;
+  constexpr int NW = kBnNW, BM = kBnBM, DMAW = kBnDmaW;
   const unsigned short* __restrict__ Bm = reinterpret_cast<const unsigned short*>(p.B);
   const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int ntm = (p.M + BM - 1) / BM, ntn = (p.N + kBnBN - 1) / kBnBN;
@@ -839,36 +496,30 @@ __global__ __launch_bounds__(64 * NWV) void gemm_bf16_nt_kernel(GemmParams p) {
   dma_b(1, 1);     // unconditional, like every prefetch below: chunks past KC read clamped
   load_a(1, raB);  // weights into a free buffer and zeros for A
   // chunk c + 1's weights -> every wave: wait for this wave's DMA(c+1) (younger: A(c+1),
-  // DMA(c+2), A(c+2)), then a bare s_barrier (a __syncthreads would drain the prefetch: vmcnt(0))
+  // DMA(c+2), A(c+2)), then a bare s_barrier (a __syncthreads would drain the prefetch: vmcnt(0)).
+  // As asm, so that it keeps its place among the DMA and the A copies; after the last chunk
+  // nothing may still land (vmcnt(0)), and lgkmcnt(0): this wave's fragment reads are done.
   auto publish = [&](int c) {
-    if (DL_BN_ASMA) {   // as asm: it keeps its place among the DMA and the A copies
-      if (c + 1 < KC) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(DMAW + 4) : "memory");
-      else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-      return;
-    }
-    if (c + 1 < KC) DL_BN_VMCNT(DMAW + 2);
-    else DL_BN_VMCNT(0);                  // nothing may still land after the loop
-    __builtin_amdgcn_s_waitcnt(0xc07f);   // lgkmcnt(0): this wave's fragment reads are done
-    __builtin_amdgcn_s_barrier();
+    if (c + 1 < KC) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(DMAW + 4) : "memory");
+    else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
   };
   publish(-1);
   auto step = [&](int c, bn_u32x4 (&ra)[2]) {
-    shortx8 a0, a1;
-    if (DL_BN_ASMA) {   // chunk c's A copied here (hipcc waits for its loads right before)
-      bn_u32x4 x0, x1;
-      asm volatile("" : "=v"(x0), "=v"(x1) : "0"(ra[0]), "1"(ra[1]));
-      a0 = __builtin_bit_cast(shortx8, x0);
-      a1 = __builtin_bit_cast(shortx8, x1);
-    } else {
-      a0 = __builtin_bit_cast(shortx8, ra[0]);
-      a1 = __builtin_bit_cast(shortx8, ra[1]);
-    }
+    // Chunk c's A is copied here by an asm statement.  hipcc counts only its own loads in vmcnt
+    // (not the weight LDS-DMA, inline asm), and it hoisted a plain copy of the next step's A
+    // registers into the current step, where that load is the youngest it knows of: a vmcnt(0)
+    // drain in the middle of every chunk's MFMAs (the weights two chunks ahead included).  The
+    // asm copy stays at its step's start, after the barrier (also asm), where hipcc's wait for
+    // the chunk's A is vmcnt(2): it lets the next chunk's A loads stay in flight.
+    bn_u32x4 x0, x1;
+    asm volatile("" : "=v"(x0), "=v"(x1) : "0"(ra[0]), "1"(ra[1]));
+    shortx8 a0 = __builtin_bit_cast(shortx8, x0), a1 = __builtin_bit_cast(shortx8, x1);
     // chunk c's A in registers of their own before the next batch reuses ra
     asm volatile("" : "+v"(a0), "+v"(a1));
     dma_b(c + 2, (c + 2) % 3);
     load_a(c + 2, ra);
     const unsigned short* Bs = lds + (c % 3) * kBnPlane + cl * 32 + 8 * bn_slot(cl, kq);
-    constexpr int PF = DL_BN_PF, NB = PF + 1;
+    constexpr int PF = kBnPF, NB = PF + 1;
     shortx8 bb[NB];
 #pragma unroll
     for (int i = 0; i < PF; ++i) bb[i] = *reinterpret_cast<const shortx8*>(Bs + 512 * i);   // fragment rows 16i + cl
@@ -900,8 +551,9 @@ __global__ __launch_bounds__(64 * NWV) void gemm_bf16_nt_kernel(GemmParams p) {
     const auto c_rsrc = __builtin_amdgcn_make_buffer_rsrc(p.C, (short)0, p.M * p.ldc * EB, 0x00020000);
     const auto m_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.mask, (short)0,
                                                           EPI == EPI_MASK ? p.M * p.ldm * 2 : 0, 0x00020000);
-    // 16-B bf16 pieces need N, ldc multiples of 8 (the swapped lane holds 8 columns)
-    const bool wide = CBF16 && DL_BN_WIDE && p.N % 8 == 0 && p.ldc % 8 == 0;
+    // bf16 output as 16-B pieces where N, ldc are multiples of 8 (the swapped lane holds 8
+    // columns), else as 8-B pieces
+    const bool wide = CBF16 && p.N % 8 == 0 && p.ldc % 8 == 0;
 #pragma unroll
     for (int a = 0; a < 2; ++a) {
       const int row = r0 + 16 * a + cl;
@@ -1050,37 +702,23 @@ __global__ __launch_bounds__(64 * NWV) void gemm_bf16_nt_kernel(GemmParams p) {
   }
 }
 
-#ifndef DL_BF16_NT
-#define DL_BF16_NT 1   // forward / dX products on gemm_bf16_nt_kernel (0: the B-resident kernel)
-#endif
-
-// DL_BF16_DIRECT=0 in the environment: the LDS epilogue (A/B measurements)
-static bool bf16_direct_enabled() {
-  static const bool on = [] {
-    const char* e = getenv("DL_BF16_DIRECT");
-    return !(e && e[0] == '0');
-  }();
-  return on;
-}
-
-// true if the streamed-weight kernel takes the product (and launches it)
+// true if the streamed-weight kernel takes the product (and launches it); it reads K and the
+// leading dimensions, never k_per_split
 static bool launch_bf16_nt(const GemmParams& gp, int epi, bool cb, hipStream_t s) {
-  if (!DL_BF16_NT || epi == EPI_SPLIT || gp.K < 8 || gp.K % 8 || gp.lda % 8 || gp.ldb % 8 || gp.lda < gp.K ||
+  if (epi == EPI_SPLIT || gp.K < 8 || gp.K % 8 || gp.lda % 8 || gp.ldb % 8 || gp.lda < gp.K ||
       gp.ldb < gp.K || (epi == EPI_MASK && gp.ldm % 8) || (reinterpret_cast<uintptr_t>(gp.A) & 15) ||
       (reinterpret_cast<uintptr_t>(gp.B) & 15) || (long long)gp.M * gp.lda * 2 >= (1LL << 31))
     return false;
-  const bool direct = bf16_direct_enabled() && gp.N % 4 == 0 && gp.ldc % 4 == 0 &&
-                      (epi != EPI_MASK || gp.ldm % 4 == 0) && (long long)gp.M * gp.ldc * 4 < (1LL << 31);
-  constexpr int NWD = DL_BN_NW;   // waves a block of the register-epilogue kernel
-  const dim3 grid((unsigned)(ceil_div(gp.M, direct ? 32 * NWD : kBnBM) * ceil_div(gp.N, kBnBN))),
-      block(direct ? 64 * NWD : 512);
+  const bool direct = gp.N % 4 == 0 && gp.ldc % 4 == 0 && (epi != EPI_MASK || gp.ldm % 4 == 0) &&
+                      (long long)gp.M * gp.ldc * 4 < (1LL << 31);
+  const dim3 grid((unsigned)(ceil_div(gp.M, kBnBM) * ceil_div(gp.N, kBnBN))), block(64 * kBnNW);
   // the register epilogue needs only the ring (39,936 B instead of the 108,544-B tiles), so other
   // kernels' blocks (the side stream's index build) can share the CU
   constexpr size_t ring = 3 * kBnPlane * sizeof(unsigned short);
-#define DL_BNT(E_, C_)                                                                                     \
-  do {                                                                                                     \
-    if (direct) hipLaunchKernelGGL((gemm_bf16_nt_kernel<E_, C_, true, NWD>), grid, block, ring, s, gp);   \
-    else hipLaunchKernelGGL((gemm_bf16_nt_kernel<E_, C_>), grid, block, kBnLds, s, gp);                    \
+#define DL_BNT(E_, C_)                                                                                \
+  do {                                                                                                \
+    if (direct) hipLaunchKernelGGL((gemm_bf16_nt_kernel<E_, C_, true>), grid, block, ring, s, gp);   \
+    else hipLaunchKernelGGL((gemm_bf16_nt_kernel<E_, C_, false>), grid, block, kBnLds, s, gp);       \
   } while (0)
   if (epi == EPI_STORE) {
     if (cb) DL_BNT(EPI_STORE, true); else DL_BNT(EPI_STORE, false);
@@ -1236,9 +874,6 @@ constexpr int kD3DA = kD3AB / 1024, kD3D = kD3DA + kD3BB / 1024;      // 9 + 25 
 constexpr size_t kD3Lds = (size_t)kD3R * kD3SB;                        // 139,264 B
 static_assert(kD3AB % 1024 == 0 && kD3BB % 1024 == 0 && kD3D == 34, "whole DMA instructions per image");
 static_assert(kD3D <= 3 * kD3W, "at most three DMA instructions per wave and step");
-#ifndef DL_BF16_DW3
-#define DL_BF16_DW3 1   // 0: the two-buffer kernel above for every weight gradient
-#endif
 
 __global__ __launch_bounds__(960) void gemm_bf16_dw3_kernel(GemmParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned short lds[];   // [R stages][A image | B image]
@@ -1357,7 +992,7 @@ static bool launch_bf16_dw(const GemmParams& gp0, int splits_req, hipStream_t s)
   kps = (kps + 63) / 64 * 64;                 // the engine sums ceil(K / kps) slabs at this rounding
   gp.k_per_split = kps;
   const int splits = (int)ceil_div(gp.K > 0 ? gp.K : 1, kps);
-  if (DL_BF16_DW3 && gp.K % kD3KS == 0) {
+  if (gp.K % kD3KS == 0) {   // whole 32-row steps: the ring kernel; else the two-buffer kernel
     const int mtiles = (int)ceil_div(gp.M, kD3BM);
     hipLaunchKernelGGL(gemm_bf16_dw3_kernel, dim3((unsigned)(mtiles * splits)), dim3(64 * kD3W), kD3Lds, s, gp);
     return true;
@@ -1392,7 +1027,7 @@ __global__ __launch_bounds__(256) void transpose_bf16_kernel(const void* __restr
 
 template <int BM, int BN, int WM, int WN, bool TA, bool TB, bool FAST>
 static void launch_f32_v(const GemmParams& gp, int epi, dim3 grid, hipStream_t s) {
-  constexpr int BK = DL_GEMM_BK;
+  constexpr int BK = kGemmBK;
   constexpr int NT = 64 * WM * WN;
   switch (epi) {
     case EPI_STORE: hipLaunchKernelGGL((gemm_f32_kernel<BM, BN, WM, WN, TA, TB, EPI_STORE, BK, FAST>), grid, dim3(NT), 0, s, gp); break;
@@ -1404,10 +1039,10 @@ static void launch_f32_v(const GemmParams& gp, int epi, dim3 grid, hipStream_t s
 
 template <int BM, int BN, int WM, int WN, bool TA, bool TB>
 static void launch_f32(const GemmParams& gp, int epi, int splits, hipStream_t s) {
-  constexpr int BK = DL_GEMM_BK;
+  constexpr int BK = kGemmBK;
   const int tiles = (int)(ceil_div(gp.M, BM) * ceil_div(gp.N, BN));
   dim3 grid(tiles, 1, splits);
-  const bool fast = gp.M % BM == 0 && gp.N % BN == 0 && gp.K % BK == 0 && gp.k_per_split % BK == 0 && !DL_GEMM_GLDS;
+  const bool fast = gp.M % BM == 0 && gp.N % BN == 0 && gp.K % BK == 0 && gp.k_per_split % BK == 0;
   if (fast) launch_f32_v<BM, BN, WM, WN, TA, TB, true>(gp, epi, grid, s);
   else launch_f32_v<BM, BN, WM, WN, TA, TB, false>(gp, epi, grid, s);
 }
@@ -1466,27 +1101,6 @@ __global__ __launch_bounds__(256) void transpose_kernel(const float* __restrict_
     const int c = c0 + y, r = r0 + tx;
     if (c < cols && r < rows) dst[(long long)c * ldd + r] = t[tx][y];
   }
-}
-
-template <int BN, int EPI, bool CB>
-static void launch_bf16_kc(const GemmParams& gp, int splits, hipStream_t s) {
-  const int tiles = (int)(ceil_div(gp.M, 128) * ceil_div(gp.N, BN));
-  hipLaunchKernelGGL((gemm_bf16_kc_kernel<128, BN, 4, 1, EPI, CB>), dim3(tiles, 1, splits), dim3(256), 0, s, gp);
-}
-
-template <int BN>
-static void dispatch_bf16_kc_bn(const GemmParams& gp, int epi, int splits, bool cb, hipStream_t s) {
-  switch (epi) {
-    case EPI_STORE: cb ? launch_bf16_kc<BN, EPI_STORE, true>(gp, splits, s) : launch_bf16_kc<BN, EPI_STORE, false>(gp, splits, s); break;
-    case EPI_RELU: cb ? launch_bf16_kc<BN, EPI_RELU, true>(gp, splits, s) : launch_bf16_kc<BN, EPI_RELU, false>(gp, splits, s); break;
-    case EPI_MASK: cb ? launch_bf16_kc<BN, EPI_MASK, true>(gp, splits, s) : launch_bf16_kc<BN, EPI_MASK, false>(gp, splits, s); break;
-    default: launch_bf16_kc<BN, EPI_SPLIT, false>(gp, splits, s); break;
-  }
-}
-
-static void dispatch_bf16_kc(const GemmParams& gp, int epi, int splits, bool cb, int bn, hipStream_t s) {
-  if (bn == 208) dispatch_bf16_kc_bn<208>(gp, epi, splits, cb, s);
-  else dispatch_bf16_kc_bn<80>(gp, epi, splits, cb, s);
 }
 
 }  // namespace dl
@@ -1573,21 +1187,12 @@ extern "C" int dl_gemm_bf16(int32_t ta, int32_t tb, int32_t M, int32_t N, int32_
   splits = (int)ceil_div(K > 0 ? K : 1, kps);
   gp.c_split_stride = c_split_stride;
   hipStream_t s = as_stream(stream);
+  // Dispatch order: the dW kernels (ta = 1, tb = 0, split slabs), the streamed-weight NT kernel
+  // (ta = 0, tb = 1, not split: the tower's forward and dX are arranged into this form), then
+  // the generic kernel.  Each launcher checks its own alignment and size limits and declines
+  // what it cannot take; the generic kernel takes everything.
   if (ta && !tb && epi == EPI_SPLIT && launch_bf16_dw(gp, splits_req, s)) DL_RETURN_LAUNCH("dl_gemm_bf16");
-  if (!ta && tb && lda % 8 == 0 && ldb % 8 == 0 && ((uintptr_t)A % 16) == 0 && ((uintptr_t)B % 16) == 0 &&
-      lda >= (K + 7) / 8 * 8 && ldb >= (K + 7) / 8 * 8) {
-    // k-contiguous fast path (the tower's products are arranged into this form)
-    int kps2 = (int)ceil_div(K, splits);
-    kps2 = (kps2 + 63) / 64 * 64;
-    if (kps2 == 0) kps2 = 64;
-    gp.k_per_split = kps2;
-    const int sp2 = (int)ceil_div(K > 0 ? K : 1, kps2);
-    if (sp2 == 1 && launch_bf16_nt(gp, epi, c_bf16 != 0, s)) DL_RETURN_LAUNCH("dl_gemm_bf16");
-    if (sp2 == 1 && launch_bf16_bres(gp, epi, c_bf16 != 0, s)) DL_RETURN_LAUNCH("dl_gemm_bf16");
-    const int bn = (N + 79) / 80 * 80 <= (N + 207) / 208 * 208 ? 80 : 208;
-    dispatch_bf16_kc(gp, epi, sp2, c_bf16 != 0, bn, s);
-    DL_RETURN_LAUNCH("dl_gemm_bf16");
-  }
+  if (!ta && tb && epi != EPI_SPLIT && launch_bf16_nt(gp, epi, c_bf16 != 0, s)) DL_RETURN_LAUNCH("dl_gemm_bf16");
 #define DL_BF(TA_, TB_)                                                              \
   if (c_bf16) launch_bf16<128, 64, 4, 1, TA_, TB_, true>(gp, epi, splits, s);        \
   else launch_bf16<128, 64, 4, 1, TA_, TB_, false>(gp, epi, splits, s);

@@ -214,12 +214,8 @@ __global__ __launch_bounds__(256) void head_kernel(int B, int fm_cols, int H, co
 // reduced: ids two samples ahead, weights one ahead; only the h row load is left on
 // a sample's critical path.  DHB: dh written as bf16 (the bf16 tower's dY operand,
 // no separate cast pass).
-// H4M: float4 chunks of a hidden row per lane (2: H <= 512, 4: H <= 1024).  With DL_WDL_HEAD_PF the
-// next sample's h row is loaded while this one is reduced (a wave walks ~8 samples, each a dependent chain:
-// row -> wave sum -> loss -> gradient stores), as the wide ids (two ahead) and weights (one).
-#ifndef DL_WDL_HEAD_PF
-#define DL_WDL_HEAD_PF 0   // 1: prefetch the next sample's h row (measured neutral, C5 head 64 us both: profiles/r06f)
-#endif
+// H4M: float4 chunks of a hidden row per lane (2: H <= 512, 4: H <= 1024).  (Loading the next
+// sample's h row while this one is reduced measured neutral, C5 head 64 us both: profiles/r06f.)
 template <bool DHB, int H4M = kHeadMaxH4, bool WEIGHTED = false>
 __global__ __launch_bounds__(256) void wdl_head_kernel(int B, int Fw, int H, const int64_t* __restrict__ wide,
                                                        int wide_ld, const float* __restrict__ h, int ldh,
@@ -266,8 +262,6 @@ __global__ __launch_bounds__(256) void wdl_head_kernel(int B, int Fw, int H, con
       r[k] = (c4 < H4 && bb < B) ? *reinterpret_cast<const float4*>(hb + 4 * c4) : make_float4(0.f, 0.f, 0.f, 0.f);
     }
   };
-  float4 hn[H4M];
-  if (DL_WDL_HEAD_PF) load_h(wave, hn);
   for (int b = wave; b < B; b += nwaves) {
     const long long wr = id_n;
     float part = wv_n;
@@ -275,13 +269,7 @@ __global__ __launch_bounds__(256) void wdl_head_kernel(int B, int Fw, int H, con
     wv_n = id_n >= 0 ? w[id_n] : 0.f;
     id_nn = load_id(b + 2 * nwaves);
     float4 hh[H4M];
-    if (DL_WDL_HEAD_PF) {
-#pragma unroll
-      for (int k = 0; k < H4M; ++k) hh[k] = hn[k];
-      load_h(b + nwaves, hn);   // the next sample's row, in flight during this one
-    } else {
-      load_h(b, hh);
-    }
+    load_h(b, hh);
 #pragma unroll
     for (int k = 0; k < H4M; ++k)
       part += hh[k].x * wh[k].x + hh[k].y * wh[k].y + hh[k].z * wh[k].z + hh[k].w * wh[k].w;

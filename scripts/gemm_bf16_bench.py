@@ -16,7 +16,6 @@ bf = lambda *sh: torch.randn(*sh, device="cuda").to(torch.bfloat16)
 x0 = bf(B, 432)
 h = bf(B, 416)
 hT = bf(416, B)
-dhT = bf(416, B)
 WT = bf(400, 432)          # W^T, k-contiguous
 W1 = bf(416, 400)
 out_b = torch.zeros(B, 416, device="cuda", dtype=torch.bfloat16)
@@ -30,8 +29,6 @@ cases = {
                                     None, 0, 1, 0, s), 2 * B * 433 * 400),
     "dx_l1 mask bf16": (lambda: call("dl_gemm_bf16", 0, 1, B, 400, 400, u16(h), 416, u16(W1), 400, ptr(out_b), 416, 1, 2,
                                      u16(h), 416, 1, 0, s), 2 * B * 400 * 400),
-    "dw_l1 split64": (lambda: call("dl_gemm_bf16", 0, 1, 416, 400, B, u16(hT), B, u16(dhT), B, ptr(slab), 400, 0, 3, None, 0,
-                                   64, 416 * 400, s), 2 * B * 417 * 400),
     "dw_l1 direct (ta=1) split64": (lambda: call("dl_gemm_bf16", 1, 0, 416, 400, B, u16(h), 416, u16(out_b), 416,
                                                  ptr(slab), 400, 0, 3, None, 0, 64, 416 * 400, s), 2 * B * 417 * 400),
     "dw_l0 direct (ta=1) split85": (lambda: call("dl_gemm_bf16", 1, 0, 432, 400, B, u16(x0), 432, u16(out_b), 416,

@@ -475,6 +475,54 @@ def test_gemm_bf16_variants(hip_lib, ta, tb, epi, cbf):
     np.testing.assert_allclose(got.numpy(), ref.numpy(), rtol=tol, atol=tol)
 
 
+_GENERIC_SHAPE = (137, 70, 44)
+
+
+@pytest.fixture(scope="module")
+def generic_ops():
+    """Operands, mask and the fp64 product of the same bf16 values, built once."""
+    M, N, K = _GENERIC_SHAPE
+    g = torch.Generator().manual_seed(11)
+    A = torch.randn(M, K, generator=g).bfloat16()
+    B = torch.randn(K, N, generator=g).bfloat16()
+    mask = (torch.rand(M, N, generator=g) > 0.5).bfloat16()
+    return A, B, mask, A.double() @ B.double()
+
+
+@pytest.mark.parametrize("epi,cbf", [(0, 0), (0, 1), (1, 0), (1, 1), (2, 0), (2, 1), (3, 0)])
+@pytest.mark.parametrize("ta,tb", [(0, 0), (0, 1), (1, 0), (1, 1)])
+def test_gemm_bf16_generic_kernel(hip_lib, generic_ops, ta, tb, epi, cbf):
+    """The generic gemm_bf16_kernel in all four orientations and every epilogue, at a shape each
+    specialised path declines: lda (= K or M, unpadded) and K are no multiples of 8 (off the NT
+    kernel), M is no multiple of 8 (off the dW kernels).  Blocks are ragged in M (137 = 128 + 9)
+    and N (70 = 64 + 6) and the second 32-deep K chunk is partial (44).  splits = 3: the entry
+    rounds k_per_split 15 -> 32 and writes 2 slabs; the buffer holds 3 (the third stays zero) and
+    all are summed.  Against fp64 on the same bf16 operands, test_gemm_bf16_variants' tolerances
+    (N(0,1) operands; they hold there at K = 320)."""
+    M, N, K = _GENERIC_SHAPE
+    A, B, mask, ref = generic_ops
+    if epi == 1:
+        ref = ref.clamp_min(0)
+    if epi == 2:
+        ref = ref * mask.double()
+    Ad = (A.t().contiguous() if ta else A).cuda()
+    Bd = (B.t().contiguous() if tb else B).cuda()
+    lda = M if ta else K
+    ldb = K if tb else N
+    splits = 3 if epi == 3 else 1
+    ldc = N + 1                          # one pad column after N: must stay untouched
+    C = torch.zeros(splits, M, ldc, dtype=torch.bfloat16 if cbf else torch.float32, device="cuda")
+    C[:, :, N] = 5.0
+    md = mask.cuda()
+    call("dl_gemm_bf16", ta, tb, M, N, K, ptr(Ad), lda, ptr(Bd), ldb, ptr(C), ldc, cbf, epi,
+         ptr(md) if epi == 2 else None, N, splits, M * ldc, _s())
+    torch.cuda.synchronize()
+    got = C[:, :, :N].double().cpu().sum(0)
+    tol = 2e-2 if cbf else 1e-3          # bf16 output: one bf16 rounding (2^-8 relative)
+    np.testing.assert_allclose(got.numpy(), ref.numpy(), rtol=tol, atol=tol)
+    assert (C[:, :, N].float().cpu() == 5.0).all()
+
+
 def _engine(model, **kw):
     from deep_learning_amd.engine import CTREngine, ModelSpec
     spec = ModelSpec(model, **kw)
@@ -891,10 +939,12 @@ def test_sort_unique_matches_numpy(hip_lib, n, distinct):
                                            (1000, 300, 72, 2, 0), (129, 416, 48, 1, 1), (65536, 416, 400, 0, 0)])
 @pytest.mark.parametrize("ldc_pad", [3, 4])   # ldc % 4 == 0 (pad 4, N % 4 == 0): the register epilogue
 def test_gemm_bf16_b_resident(hip_lib, M, N, K, epi, cbf, ldc_pad):
-    """The tall-skinny bf16 path (ta=0, tb=1: the streamed-weight kernel gemm_bf16_nt_kernel,
-    the B-resident kernel where it declines): relu / ReluGrad-mask / store epilogues, bf16 or
-    f32 output, ragged M, N and K chunks (K past one chunk, not a multiple of 32, beyond the
-    B-resident limit), against an fp64 product of the same bf16 operands."""
+    """The tall-skinny bf16 path (ta=0, tb=1): every case runs the streamed-weight kernel
+    gemm_bf16_nt_kernel (K, lda and ldm are multiples of 8; the name is from the B-resident
+    kernel it replaced), with the LDS epilogue at ldc_pad = 3 and the register epilogue at 4
+    (where N % 4 == 0): relu / ReluGrad-mask / store epilogues, bf16 or f32 output, ragged M, N and K chunks (K of
+    one chunk, past one chunk, not a multiple of 32), against an fp64 product of the same bf16
+    operands."""
     g = torch.Generator().manual_seed(M + N + K)
     lda = (K + 7) // 8 * 8 + 8
     A = torch.randn(M, lda, generator=g).bfloat16()

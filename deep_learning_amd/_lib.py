@@ -200,6 +200,9 @@ SIGNATURES = {
     "dl_wide_seg_grad": (I32, [P, I32, P, P, P, I64, I64, P, P, P, P]),
     "dl_wide_rec_update": (I32, [P, P, I64, P, P, I32, I32, F, P, I32, P, P, P, P, P, P]),
     "dl_wide_rec_flush": (I32, [P, I64, F, P, I32, P, P, P, P]),
+    "dl_wide_ftrl_gather": (I32, [P, I64, P, P, I64, I32, I32, P, P, P, P]),
+    "dl_wide_ftrl_update": (I32, [P, P, I64, P, P, I32, I32, F, F, F, P, P, P]),
+    "dl_ftrl_rows": (I32, [P, P, P, P, P, I64, F, F, F, P, P]),
     "dl_comm_unique_id_bytes": (I32, []),
     "dl_comm_get_unique_id": (I32, [P]),
     "dl_comm_init": (I32, [P, I32, I32, P]),

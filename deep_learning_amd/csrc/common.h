@@ -147,6 +147,24 @@ __device__ __forceinline__ void adam_elem_sparse(float& p, float& m, float& v, f
   p = p - adam_step_size(m, v, alpha, eps);
 }
 
+// One TF1 ApplyFtrl element update (training_ops.cc ApplyFtrl / SparseApplyFtrl with
+// learning_rate_power = -0.5 and no shrinkage; z = linear, n = accum):
+//   n' = n + g^2;  z += g - (sqrt(n') - sqrt(n)) / lr * w;
+//   w = |z| > l1 ? (sign(z) l1 - z) / (sqrt(n') / lr + 2 l2) : 0
+// Shared by the record path and the plane sweep (wide.hip) so the two compile to the same
+// float operations: bit-identical by construction, as adam_elem's paths are.  The square
+// roots and divisions are the correctly rounded ones: the step runs once per touched row (no
+// replay loop to bound), and sqrt(n') - sqrt(n) cancels.
+__device__ __forceinline__ void ftrl_elem(float& w, float& z, float& n, float g, float lr, float l1, float l2) {
+#pragma clang fp contract(off)
+  const float n1 = n + g * g;
+  const float r1 = sqrtf(n1);
+  const float sigma = (r1 - sqrtf(n)) / lr;
+  z = z + (g - sigma * w);
+  w = fabsf(z) > l1 ? (copysignf(l1, z) - z) / (r1 / lr + 2.f * l2) : 0.f;
+  n = n1;
+}
+
 // ---------------------------------------------------------------------------
 // Embedding-table Adam state in the root form: the table keeps s = sqrt(v) in place of v
 // (records, the dense table sweep, the gather's moment stash; the host converts at the

@@ -22,6 +22,10 @@
 //                        L2 loss term of these rows (pre-update w^2) into sq_out
 //   dl_wide_rec_flush    every row caught up to step t (the flush schedule, exports); the L2
 //                        loss term of the rows the last step did not touch comes with it
+//
+// FTRL-proximal (wide_optimizer = "ftrl") is the second optimizer of the same rows, below the
+// Adam forms: dl_wide_ftrl_gather / dl_wide_ftrl_update on records {w, z, n, 0}, dl_ftrl_rows on
+// the dense engine's planes.
 #include "common.h"
 
 namespace dl {
@@ -296,6 +300,110 @@ __global__ __launch_bounds__(256) void wide_seg_long_kernel(const float* __restr
   }
 }
 
+// ---------------------------------------------------------------------------
+// FTRL-proximal for the wide weights (ModelSpec.wide_optimizer = "ftrl"; TF1 FtrlOptimizer with
+// learning_rate_power = -0.5, initial accumulator 0.1, l1 / l2, no shrinkage: ftrl_elem).  The
+// regularisers live in the proximal step, so a row the batch does not touch does not move:
+// record {w, z, n, 0} with no stamp, no alpha ring, no replay and no flush — the same random
+// accesses as the Adam forms above, the same wloc / stash / gloc / dmark protocol.
+
+// Unique wide rows u < n_uniq (rows uniq[u]) and the H deep-output rows Fw + j as they stand:
+// wloc[Fw + j] / wloc[Fw + H + u] = w; stash[u] = (w, z, n, row bits) (row bits -1: a faulted row).
+__global__ __launch_bounds__(256) void wide_ftrl_gather_kernel(const float4* __restrict__ rec, long long w_rows,
+                                                               const uint32_t* __restrict__ uniq,
+                                                               const int32_t* __restrict__ n_uniq, long long max_u,
+                                                               int Fw, int H, const float* __restrict__ opt,
+                                                               float* __restrict__ wloc, float4* __restrict__ stash) {
+  const long long nu = n_uniq ? (long long)min((long long)max(n_uniq[0], 0), max_u) : max_u;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < H + nu;
+       i += (long long)gridDim.x * blockDim.x) {
+    const long long row = i < H ? Fw + i : (long long)uniq[i - H];
+    if (row < 0 || row >= w_rows) {
+      raise_fault(opt_status(opt), DL_STATUS_INDEX);
+      if (i >= H && stash) stash[i - H] = make_float4(0.f, 0.f, 0.f, __int_as_float(-1));
+      continue;
+    }
+    const float4 r = rec[row * kWideRecF4];
+    wloc[Fw + i] = r.x;   // i < H: the deep-output row Fw + i; else local row Fw + H + u
+    if (i >= H && stash) stash[i - H] = make_float4(r.x, r.y, r.z, __int_as_float((int)row));
+  }
+}
+
+// Pass A: the batch's unique wide rows.  g = its wide terms + its deep-output term when the row
+// is one of Fw..Fw+H (exact int64 sum), the FTRL step from the stashed state, record written.
+// Deep-output rows it covered are marked for pass B.
+__global__ __launch_bounds__(256) void wide_ftrl_update_kernel(float4* __restrict__ rec, const int32_t* __restrict__ n_uniq,
+                                                               long long max_u, const float4* __restrict__ stash,
+                                                               long long* __restrict__ gloc, int Fw, int H, float lr,
+                                                               float l1, float l2, const float* __restrict__ opt,
+                                                               uint8_t* __restrict__ dmark) {
+  const bool skip = step_poisoned(opt);
+  const long long nu = (long long)min((long long)max(n_uniq[0], 0), max_u);
+  for (long long u = (long long)blockIdx.x * blockDim.x + threadIdx.x; u < nu; u += (long long)gridDim.x * blockDim.x) {
+    const float4 s = stash[u];
+    const long long row = (long long)__float_as_int(s.w);
+    long long q = gloc[Fw + H + u];
+    gloc[Fw + H + u] = 0;
+    const bool deep = row >= Fw && row < Fw + H;
+    if (deep) {
+      q += gloc[row];   // the deep-output term of the same row (pass B resets it)
+      dmark[row - Fw] = 1;
+    }
+    if (skip || row < 0) continue;
+    float w = s.x, z = s.y, n = s.z;
+    ftrl_elem(w, z, n, wide_float(q), lr, l1, l2);
+    wide_rec_store(rec, row, make_float4(w, z, n, 0.f));
+  }
+}
+
+// Pass B: the H deep-output rows pass A did not cover (their gradient: the deep term alone).
+__global__ __launch_bounds__(256) void wide_ftrl_update_deep_kernel(float4* __restrict__ rec, long long* __restrict__ gloc,
+                                                                    int Fw, int H, float lr, float l1, float l2,
+                                                                    const float* __restrict__ opt,
+                                                                    uint8_t* __restrict__ dmark) {
+  const bool skip = step_poisoned(opt);
+  for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < H; j += gridDim.x * blockDim.x) {
+    const long long row = Fw + j;
+    const long long q = gloc[row];
+    gloc[row] = 0;
+    if (dmark[j]) {   // updated in pass A with the batch's wide terms
+      dmark[j] = 0;
+      continue;
+    }
+    if (skip) continue;
+    float4 r = rec[row * kWideRecF4];
+    ftrl_elem(r.x, r.y, r.z, wide_float(q), lr, l1, l2);
+    wide_rec_store(rec, row, make_float4(r.x, r.y, r.z, 0.f));
+  }
+}
+
+// The same step on the flagged rows of the plane arrays (the dense engine: w, z, n one float per
+// row, the head's fixed-point gradient and touched flags, both reset here): one thread per 4
+// rows; w, z, n of an unflagged group are neither read nor written.
+__global__ __launch_bounds__(256) void ftrl_rows_kernel(float* __restrict__ w, float* __restrict__ z,
+                                                        float* __restrict__ n, long long* __restrict__ g,
+                                                        uint8_t* __restrict__ touched, long long rows, float lr,
+                                                        float l1, float l2, const float* __restrict__ opt) {
+  const bool skip = step_poisoned(opt);
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < (rows + 3) / 4;
+       i += (long long)gridDim.x * blockDim.x) {
+    const long long r0 = 4 * i;
+    if (r0 + 4 <= rows) {
+      if (reinterpret_cast<const uint32_t*>(touched)[i] == 0) continue;
+    }
+    for (long long r = r0; r < min(r0 + 4, rows); ++r) {
+      if (!touched[r]) continue;
+      touched[r] = 0;
+      const float gr = wide_float(g[r]);
+      g[r] = 0;
+      if (skip) continue;
+      float wi = w[r], zi = z[r], ni = n[r];
+      ftrl_elem(wi, zi, ni, gr, lr, l1, l2);
+      w[r] = wi; z[r] = zi; n[r] = ni;
+    }
+  }
+}
+
 static unsigned wide_grid(long long n) {   // grid-stride kernels, one regulariser atomic per block
   long long b = (n + 255) / 256;
   if (b > kSumGrid) b = kSumGrid;
@@ -361,6 +469,54 @@ extern "C" int dl_wide_rec_update(float* rec, const int32_t* n_uniq, int64_t max
                        reinterpret_cast<long long*>(gloc), Fw, H, l2, hist, hist_len, opt, dmark,
                        sq_out ? sq_out + (max_uniq > 0 ? wide_rows_grid(max_uniq) : 0) : nullptr, acc);
   DL_RETURN_LAUNCH("dl_wide_rec_update");
+}
+
+extern "C" int dl_wide_ftrl_gather(const float* rec, int64_t w_rows, const uint32_t* uniq_rows, const int32_t* n_uniq,
+                                   int64_t max_uniq, int32_t Fw, int32_t H, const float* opt, float* wloc, float* stash,
+                                   void* stream) {
+  DL_CHECK_ARG(rec && opt && wloc && (max_uniq <= 0 || uniq_rows), "NULL argument");
+  DL_CHECK_ARG(Fw >= 0 && H >= 0 && (long long)Fw + H <= w_rows, "bad Fw / H");
+  DL_CHECK_ARG(((uintptr_t)rec % 16) == 0 && ((uintptr_t)stash % 16) == 0, "rec / stash must be 16-B aligned");
+  const long long n = H + (max_uniq > 0 ? max_uniq : 0);
+  if (n == 0) return 0;
+  hipLaunchKernelGGL(wide_ftrl_gather_kernel, dim3(wide_rows_grid(n)), dim3(256), 0, as_stream(stream),
+                     reinterpret_cast<const float4*>(rec), (long long)w_rows, uniq_rows, n_uniq,
+                     (long long)(max_uniq > 0 ? max_uniq : 0), Fw, H, opt, wloc, reinterpret_cast<float4*>(stash));
+  DL_RETURN_LAUNCH("dl_wide_ftrl_gather");
+}
+
+static bool ftrl_hyper_ok(float lr, float l1, float l2) {
+  return lr > 0.f && l1 >= 0.f && l2 >= 0.f && lr < INFINITY && l1 < INFINITY && l2 < INFINITY;
+}
+
+extern "C" int dl_wide_ftrl_update(float* rec, const int32_t* n_uniq, int64_t max_uniq, const float* stash,
+                                   int64_t* gloc, int32_t Fw, int32_t H, float lr, float l1, float l2, const float* opt,
+                                   uint8_t* dmark, void* stream) {
+  DL_CHECK_ARG(rec && gloc && opt && dmark && (max_uniq <= 0 || (n_uniq && stash)), "NULL argument");
+  DL_CHECK_ARG(Fw >= 0 && H >= 0, "bad Fw / H");
+  DL_CHECK_ARG(ftrl_hyper_ok(lr, l1, l2), "lr must be finite and > 0, l1 / l2 finite and >= 0");
+  DL_CHECK_ARG(((uintptr_t)rec % 16) == 0 && ((uintptr_t)stash % 16) == 0, "rec / stash must be 16-B aligned");
+  hipStream_t s = as_stream(stream);
+  if (max_uniq > 0)
+    hipLaunchKernelGGL(wide_ftrl_update_kernel, dim3(wide_rows_grid(max_uniq)), dim3(256), 0, s,
+                       reinterpret_cast<float4*>(rec), n_uniq, (long long)max_uniq,
+                       reinterpret_cast<const float4*>(stash), reinterpret_cast<long long*>(gloc), Fw, H, lr, l1, l2,
+                       opt, dmark);
+  if (H > 0)
+    hipLaunchKernelGGL(wide_ftrl_update_deep_kernel, dim3(wide_rows_grid(H)), dim3(256), 0, s,
+                       reinterpret_cast<float4*>(rec), reinterpret_cast<long long*>(gloc), Fw, H, lr, l1, l2, opt, dmark);
+  DL_RETURN_LAUNCH("dl_wide_ftrl_update");
+}
+
+extern "C" int dl_ftrl_rows(float* w, float* z, float* n, int64_t* g_fixed, uint8_t* touched, int64_t rows, float lr,
+                            float l1, float l2, const float* opt, void* stream) {
+  DL_CHECK_ARG(w && z && n && g_fixed && touched && opt, "NULL argument");
+  DL_CHECK_ARG(ftrl_hyper_ok(lr, l1, l2), "lr must be finite and > 0, l1 / l2 finite and >= 0");
+  DL_CHECK_ARG(((uintptr_t)touched % 4) == 0, "touched must be 4-B aligned");
+  if (rows <= 0) return 0;
+  hipLaunchKernelGGL(ftrl_rows_kernel, dim3(wide_rows_grid((rows + 3) / 4)), dim3(256), 0, as_stream(stream), w, z, n,
+                     reinterpret_cast<long long*>(g_fixed), touched, (long long)rows, lr, l1, l2, opt);
+  DL_RETURN_LAUNCH("dl_ftrl_rows");
 }
 
 extern "C" int dl_wide_rec_flush(float* rec, int64_t w_rows, float l2, const float* hist, int32_t hist_len,

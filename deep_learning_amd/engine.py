@@ -85,6 +85,10 @@ class ModelSpec:
     cross_layers: layers of a Deep & Cross network (test_model/DCN.py:73-96) on the tower input of
     the dnn_pipeline / dnn_cate / dnn_multi / dnn_multi_cate models, its output joining the tower's
     in the one output layer (parameters cross_layer_%d, cross_bias_%d, cross_res); 0: none.
+    wide_optimizer: "adam" (the reference's one optimizer) or "ftrl" (wdl only): wdl_weights trained
+    by TF1 FtrlOptimizer(wide_lr, learning_rate_power=-0.5, initial_accumulator_value=0.1,
+    l1_regularization_strength=wide_l1, l2_regularization_strength=wide_l2), the loss's L2 term on
+    wdl_weights dropped; wide_lr None: lr, and never decayed.
     """
 
     CROSS_MODELS = ("dnn_pipeline", "dnn_cate", "dnn_multi", "dnn_multi_cate")
@@ -93,9 +97,22 @@ class ModelSpec:
     def __init__(self, model, C=13, V=0, S=26, E=16, cate_index_size=1000, hidden=(400, 400, 400),
                  multi_ranges=(), Fw=0, lr=0.001, l2=1e-5, decay_steps=10000000, decay_rate=0.9,
                  beta1=0.9, beta2=0.999, eps=1e-8, logloss_eps=1e-7, tower="f32", dropout_keep_deep=None,
-                 dropout_keep_fm=None, pos_weight=1.0, cross_layers=0):
+                 dropout_keep_fm=None, pos_weight=1.0, cross_layers=0, wide_optimizer="adam", wide_lr=None,
+                 wide_l1=0.0, wide_l2=0.0):
         if model not in FAMILIES:
             raise ValueError("unsupported model %r" % model)
+        if wide_optimizer not in ("adam", "ftrl"):
+            raise ValueError("wide_optimizer must be 'adam' or 'ftrl', got %r" % (wide_optimizer,))
+        if wide_optimizer == "ftrl" and model != "wdl":
+            raise ValueError("wide_optimizer='ftrl': only wdl has wide weights, not %s" % model)
+        for k, v, ok in (("wide_lr", wide_lr, lambda x: x > 0.0), ("wide_l1", wide_l1, lambda x: x >= 0.0),
+                         ("wide_l2", wide_l2, lambda x: x >= 0.0)):
+            if v is not None and not (math.isfinite(float(v)) and ok(float(v))):
+                raise ValueError("wide_optimizer: %s must be finite and %s 0, got %r"
+                                 % (k, ">" if k == "wide_lr" else ">=", v))
+        self.wide_optimizer = wide_optimizer
+        self.wide_lr = None if wide_lr is None else float(wide_lr)
+        self.wide_l1, self.wide_l2 = float(wide_l1), float(wide_l2)
         if int(cross_layers) != cross_layers or cross_layers < 0:
             raise ValueError("cross_layers must be an integer >= 0, got %r" % (cross_layers,))
         self.cross_layers = int(cross_layers)
@@ -152,6 +169,11 @@ class ModelSpec:
             if self.cross_layers > self.CROSS_MAX_LAYERS or self.deep_in > self.CROSS_MAX_IN:
                 raise ValueError("cross_layers: at most %d layers on at most %d tower-input columns, got %d on %d"
                                  % (self.CROSS_MAX_LAYERS, self.CROSS_MAX_IN, self.cross_layers, self.deep_in))
+
+    @property
+    def ftrl_lr(self):
+        """FTRL's constant learning rate: wide_lr, or the model's (undecayed) learning rate."""
+        return float(self.lr if self.wide_lr is None else self.wide_lr)
 
     @property
     def dropout(self):
@@ -293,6 +315,9 @@ class CTREngine:
         if self.weighted and type(self) is not CTREngine:
             raise ValueError("sample_weight / pos_weight: not supported by %s (the loss normaliser, the batch's "
                              "nonzero-weight count, would need an all-reduce across the ranks)" % type(self).__name__)
+        if spec.wide_optimizer == "ftrl" and type(self) is not CTREngine:
+            raise ValueError("wide_optimizer='ftrl': not supported by %s (its owner-side wide update is Adam's)"
+                             % type(self).__name__)
         if not torch.cuda.is_available():
             raise _lib.DLError("CTREngine needs a HIP device (no CPU fallback)")
         _lib.lib()
@@ -396,6 +421,9 @@ class CTREngine:
         self.opt = z(_lib.OPT_LEN)   # include/dlamd.h: Adam scalars, per-step sums, status word
         self.opt[:8].copy_(torch.tensor([sp.beta1, sp.beta2, sp.lr, 0.0, sp.beta1, sp.beta2, sp.eps, 0.0]))
         self.wdl = sp.model == "wdl"
+        # FTRL-proximal on wdl_weights (ModelSpec.wide_optimizer, wide.hip): wm / wv (the records'
+        # second and third floats) hold FTRL's z and n; no flush, no wide L2 loss term
+        self.ftrl = sp.wide_optimizer == "ftrl"
         if self.wdl:   # wdl_weights [N + H] (deep-output rows alias wide ids, wdl.py:241-248) + bias
             self.w_rows = N + sp.hidden[-1]
             wr = _ru(self.w_rows, 16)
@@ -411,6 +439,7 @@ class CTREngine:
         # over all N + H rows (wdl.py:270-271); bit-identical to it.  DLAMD_WIDE_LAZY=0: dense.
         self.wide_lazy = bool(self.wdl and self.lazy and type(self) is CTREngine
                               and os.environ.get("DLAMD_WIDE_LAZY", "1") != "0")
+        self.wide_flushes = self.wide_lazy and not self.ftrl   # Adam's records lag and need catching up
         if self.wide_lazy:
             Fw, Hh, Bm = sp.Fw, sp.hidden[-1], max_batch
             nw = Bm * Fw
@@ -663,6 +692,7 @@ class CTREngine:
                  math.sqrt(2.0 / self.w_rows), seed + 3, 0, s)                           # wdl.py:241-244
             self.ww[self.w_rows:].zero_()
             self.wb[0] = float(np.random.default_rng(seed).standard_normal())
+            self._ftrl_reset()
         if not sp.xavier_table:
             call("dl_init_random", ptr(self.table), self.table.numel(), 0, 0.0, 0.01, seed, 0, s)
         if self.first is not None:
@@ -741,9 +771,11 @@ class CTREngine:
             self.ww[: self.w_rows].copy_(torch.from_numpy(np.ascontiguousarray(P["wdl_weights"][:, 0], np.float32)))
             self.wb.zero_()
             self.wb[:1].copy_(torch.from_numpy(np.asarray(P["wdl_bias"], np.float32).reshape(-1)))
+            self._load_ftrl(P)
             if self.wide_lazy:
-                self.wm.zero_()
-                self.wv.zero_()
+                if not self.ftrl:
+                    self.wm.zero_()
+                    self.wv.zero_()
                 self._wide_pack()
             torch.cuda.synchronize()
             return
@@ -815,25 +847,79 @@ class CTREngine:
     def dense_params(self):
         """The dense parameters (hidden layers, head or wdl weights + bias) in the reference
         layout (numpy); the wide records are caught up first."""
-        return self._export_dense(self.W, self.w_head, self._wide_state()[0], getattr(self, "wb", None),
-                                  getattr(self, "cw", None))
+        ww, wz, wn = self._wide_state()
+        P = self._export_dense(self.W, self.w_head, ww, getattr(self, "wb", None), getattr(self, "cw", None))
+        if self.ftrl:
+            P.update(self._ftrl_export(wz, wn))
+        return P
 
     def dense_state(self):
         """Adam moments of the dense parameters (hidden layers, head / wdl weights) in the
         reference layout: {"m": {key: array}, "v": {key: array}} (tests; the table's are in
         adam_state())."""
         _, wm, wv = self._wide_state()
+        if self.ftrl:   # no Adam moments of wdl_weights: FTRL's z and n under their own names
+            d = {"m": self._export_dense(self.Wm, self.hm, None, self.wbm, None),
+                 "v": self._export_dense(self.Wv, self.hv, None, self.wbv, None)}
+            d.update(self._ftrl_export(wm, wv))
+            return d
         return {"m": self._export_dense(self.Wm, self.hm, wm, getattr(self, "wbm", None), getattr(self, "cm", None)),
                 "v": self._export_dense(self.Wv, self.hv, wv, getattr(self, "wbv", None), getattr(self, "cv", None))}
 
     # ------------------------------------------------------------------ wide records (wdl)
+    FTRL_KEYS = ("ftrl/z", "ftrl/n")   # FTRL's linear and accumulator state of wdl_weights, [N + H, 1]
+    FTRL_N0 = 0.1                      # initial_accumulator_value
+
+    def _ftrl_reset(self):
+        """FTRL's initial state in the planes: z = 0, n = 0.1 (nothing for Adam)."""
+        if self.ftrl:
+            self.wm.zero_()
+            self.wv.zero_()
+            self.wv[: self.w_rows].fill_(self.FTRL_N0)
+
+    def _ftrl_export(self, wz, wn):
+        return {"ftrl/z": wz[: self.w_rows].cpu().numpy()[:, None].copy(),
+                "ftrl/n": wn[: self.w_rows].cpu().numpy()[:, None].copy()}
+
+    def _ftrl_check(self, d, what):
+        """Whether d carries FTRL's state; a state of the other wide optimizer is refused."""
+        has = [k in d for k in self.FTRL_KEYS]
+        if any(has) and not self.ftrl:
+            raise ValueError("%s holds FTRL state (%s) of wdl_weights, but this engine has wide_optimizer='adam'"
+                             % (what, ", ".join(self.FTRL_KEYS)))
+        if self.ftrl and any(has) and not all(has):
+            raise ValueError("%s: wide_optimizer='ftrl' needs both %s" % (what, " and ".join(self.FTRL_KEYS)))
+        return all(has)
+
+    def _load_ftrl(self, P, what="load_params"):
+        """FTRL's z and n from P into the planes (absent: the initial state)."""
+        if not self._ftrl_check(P, what) or not self.ftrl:
+            self._ftrl_reset()
+            return
+        for k, t in zip(self.FTRL_KEYS, (self.wm, self.wv)):
+            a = np.ascontiguousarray(P[k], np.float32).reshape(-1)
+            if a.size != self.w_rows:
+                raise ValueError("%s holds %d values for %d wdl_weights rows" % (k, a.size, self.w_rows))
+            t.zero_()
+            t[: self.w_rows].copy_(torch.from_numpy(a))
+
+    def wide_nonzero(self):
+        """Rows of wdl_weights with w != 0 (FTRL's L1 leaves the others at exactly zero)."""
+        if not self.wdl:
+            raise ValueError("wide_nonzero: only wdl has wide weights")
+        w = self._wide_state()[0]
+        return int((w[: self.w_rows] != 0).sum().item())
+
     def _wide_pack(self):
-        """Dense wdl_weights (+ moments) -> records {w, m, v, stamp = current step}."""
+        """Dense wdl_weights (+ moments) -> records {w, m, v, stamp = current step}; FTRL:
+        {w, z, n, 0}."""
         n = self.ww.shape[0]
         self.wrec.zero_()
         self.wrec[:n, 0].copy_(self.ww)
         self.wrec[:n, 1].copy_(self.wm)
         self.wrec[:n, 2].copy_(self.wv)
+        if self.ftrl:
+            return
         self.wrec.view(torch.int32)[:, 3] = int(self.opt[7].item())
         self._wsq_step = -1
 
@@ -843,7 +929,8 @@ class CTREngine:
             return None, None, None
         if not self.wide_lazy:
             return self.ww, self.wm, self.wv
-        self._wide_flush()
+        if self.wide_flushes:
+            self._wide_flush()
         return self.wrec[:, 0], self.wrec[:, 1], self.wrec[:, 2]
 
     def _wide_flush(self):
@@ -872,7 +959,8 @@ class CTREngine:
             P["deep_%d" % l] = W.copy()
             P["deep_bias_%d" % l] = Wi[dims[l], : dims[l + 1]][None, :].copy()
         if self.wdl:
-            P["wdl_weights"] = ww[: self.w_rows].cpu().numpy()[:, None].copy()
+            if ww is not None:
+                P["wdl_weights"] = ww[: self.w_rows].cpu().numpy()[:, None].copy()
             P["wdl_bias"] = wb[:1].cpu().numpy().copy()
             return P
         wi = head[: self.head_n].cpu().numpy()
@@ -929,7 +1017,7 @@ class CTREngine:
                 self.rec.shape[0], ptr(self.hist), self.hist_len, ptr(self.opt), ptr(pp), ptr(w1),
                 _lib.stream_handle())
         self.planes_step = self.steps if planes else getattr(self, "planes_step", -1)
-        if getattr(self, "wide_lazy", False):
+        if getattr(self, "wide_flushes", False):
             self._wide_flush()
         self.since_flush = 0
 
@@ -1011,24 +1099,36 @@ class CTREngine:
     def adam_state(self):
         """Table Adam state in the dense layout (tests, checkpoints): dict of m, v (+ m1, v1) as
         numpy.  The device keeps the root state s = sqrt(v) (csrc/common.h adam_elem_root);
-        v is exported as fl(s * s)."""
+        v is exported as fl(s * s).  With wide_optimizer="ftrl" the wide weights' z and n come
+        along as "ftrl/z", "ftrl/n"."""
         E, N = self.spec.E, self.N
+        ftrl = self._ftrl_export(*self._wide_state()[1:]) if self.ftrl else {}
         if not self.lazy:
             d = {"m": self.tm[:N].cpu().numpy(), "v": _root_to_v(self.tv[:N])}
             if self.first is not None:
                 d["m1"], d["v1"] = self.fmm[:N].cpu().numpy(), _root_to_v(self.fmv[:N])
-            return d
+            return dict(d, **ftrl)
         self.flush()
         r = self.rec[:N]
         d = {"m": r[:, E + 4: 2 * E + 4].cpu().numpy(), "v": _root_to_v(r[:, 2 * E + 4: 3 * E + 4])}
         if self.spec.fm:
             d["m1"], d["v1"] = r[:, E + 1].cpu().numpy(), _root_to_v(r[:, E + 2])
-        return d
+        return dict(d, **ftrl)
 
     def set_adam_state(self, d):
         """Inverse of adam_state() (v imported as s = fl(sqrt(v))); for records, stamps the rows
-        with the current step."""
+        with the current step.  A state of the other wide optimizer (FTRL's z / n into an Adam
+        engine, or none of them into an FTRL engine) is refused."""
         E, N = self.spec.E, self.N
+        if not self._ftrl_check(d, "set_adam_state") and self.ftrl:
+            raise ValueError("set_adam_state: an Adam-mode state (no %s) cannot restore an engine with "
+                             "wide_optimizer='ftrl'" % ", ".join(self.FTRL_KEYS))
+        if self.ftrl:
+            self._load_ftrl(d, "set_adam_state")
+            if self.wide_lazy:
+                n = self.ww.shape[0]
+                self.wrec[:n, 1].copy_(self.wm)
+                self.wrec[:n, 2].copy_(self.wv)
         t = lambda k: torch.from_numpy(np.ascontiguousarray(d[k], np.float32)).to(self.dev)
         s = lambda k: torch.from_numpy(_v_to_root(d[k])).to(self.dev)
         if not self.lazy:
@@ -1261,10 +1361,15 @@ class CTREngine:
             # the batch's wide rows caught up into the compact local table, the head on local ids
             fn, dh_last = ("dl_wdl_head_fwd_bwd_bf16", self.dhb[-1]) if self.bf else ("dl_wdl_head_fwd_bwd", self.dh[-1])
             nw = B * sp.Fw
-            self._c("wide_gather", "dl_wide_rec_gather", ptr(self.wrec), self.w_rows, ptr(self.widx_uniq),
-                    ptr(self.widx_n), nw, sp.Fw, H, ptr(self.hist), self.hist_len, ptr(self.opt), sp.l2,
-                    1 if train else 0, ptr(self.wloc), ptr(self.wstash) if train else None,
-                    ptr(self.wrep) if train else None, s)
+            if self.ftrl:   # the records as they stand: FTRL rows never lag
+                self._c("wide_gather", "dl_wide_ftrl_gather", ptr(self.wrec), self.w_rows, ptr(self.widx_uniq),
+                        ptr(self.widx_n), nw, sp.Fw, H, ptr(self.opt), ptr(self.wloc),
+                        ptr(self.wstash) if train else None, s)
+            else:
+                self._c("wide_gather", "dl_wide_rec_gather", ptr(self.wrec), self.w_rows, ptr(self.widx_uniq),
+                        ptr(self.widx_n), nw, sp.Fw, H, ptr(self.hist), self.hist_len, ptr(self.opt), sp.l2,
+                        1 if train else 0, ptr(self.wloc), ptr(self.wstash) if train else None,
+                        ptr(self.wrep) if train else None, s)
             self._c("head", fn + sw, B, sp.Fw, H, ptr(self.in_wide_loc), sp.Fw, ptr(self.h[-1]), self.h_ld[-1],
                     ptr(self.wloc), ptr(self.wb), sp.Fw + H + nw, ptr(self.in_label), sp.logloss_eps, *scale,
                     ptr(self.score), ptr(self.z), ptr(self.dz), ptr(dh_last), None, None,
@@ -1560,6 +1665,11 @@ class CTREngine:
                     None, s)
             self._c("adam_bias", "dl_adam_dense", ptr(self.wb), ptr(self.wbm), ptr(self.wbv),
                     ptr(self.head_slab[:, H:]), hb, H + 2, 1, 0.0, 0, ptr(self.opt), None, None, s)
+            if self.ftrl:   # FTRL-proximal on the same rows: nothing joins the step's regulariser sum
+                self._c("ftrl_wide", "dl_wide_ftrl_update", ptr(self.wrec), ptr(self.widx_n), B * sp.Fw,
+                        ptr(self.wstash), ptr(self.wgloc), sp.Fw, H, sp.ftrl_lr, sp.wide_l1, sp.wide_l2, ptr(self.opt),
+                        ptr(self.wdmark), s)
+                return
             self._c("adam_wide", "dl_wide_rec_update", ptr(self.wrec), ptr(self.widx_n), B * sp.Fw, ptr(self.wstash),
                     ptr(self.wgloc), sp.Fw, H, sp.l2, ptr(self.hist), self.hist_len, ptr(self.opt), ptr(self.wdmark),
                     ptr(self.wsq_part), ptr(self.wrep), ptr(self.wacc), s)
@@ -1571,9 +1681,13 @@ class CTREngine:
                     ptr(self.w_touched), s)
             self._c("adam_bias", "dl_adam_dense", ptr(self.wb), ptr(self.wbm), ptr(self.wbv),
                     ptr(self.head_slab[:, H:]), hb, H + 2, 1, 0.0, 0, ptr(self.opt), None, None, s)
-            self._c("adam_wide", "dl_adam_rows", ptr(self.ww), ptr(self.wm), ptr(self.wv), ptr(self.wg),
-                    ptr(self.w_touched), self.ww.shape[0], 1, sp.l2, 1 | _lib.ROWS_GRAD_FIXED, ptr(self.opt),
-                    ptr(self.opt[8:]), s)
+            if self.ftrl:   # FTRL-proximal on the flagged rows of the planes (wm: z, wv: n)
+                self._c("ftrl_wide", "dl_ftrl_rows", ptr(self.ww), ptr(self.wm), ptr(self.wv), ptr(self.wg),
+                        ptr(self.w_touched), self.ww.shape[0], sp.ftrl_lr, sp.wide_l1, sp.wide_l2, ptr(self.opt), s)
+            else:
+                self._c("adam_wide", "dl_adam_rows", ptr(self.ww), ptr(self.wm), ptr(self.wv), ptr(self.wg),
+                        ptr(self.w_touched), self.ww.shape[0], 1, sp.l2, 1 | _lib.ROWS_GRAD_FIXED, ptr(self.opt),
+                        ptr(self.opt[8:]), s)
             if self.lazy:
                 return
             self._c("adam_table", "dl_adam_rows", ptr(self.table), ptr(self.tm), ptr(self.tv), ptr(self.tg),
@@ -1852,7 +1966,7 @@ class CTREngine:
         if sp.hidden_reg == "l1":   # l1_regularizer: scale * sum |W| (dnn.py:88-90)
             return data + sp.l2 * _lib.reg_sum(self.opt)
         reg = _lib.reg_sum(self.opt)
-        if getattr(self, "wide_lazy", False):
+        if getattr(self, "wide_flushes", False):
             # the wide rows the step left untouched: their L2 term from a flush (wide.hip); the
             # touched rows' from the update's block partials — only the blocks this batch size
             # launched (a smaller last batch leaves an earlier batch's partials beyond them)
@@ -1867,7 +1981,7 @@ class CTREngine:
         regulariser terms on the device (dl_loss_accumulate), and with lazy wide records their
         L2 term arrives as the records are applied (the wide table is flushed first, so every
         replayed step from here on belongs to the sum)."""
-        if getattr(self, "wide_lazy", False):
+        if getattr(self, "wide_flushes", False):
             self._wide_flush()
             self.wacc.zero_()
         self.loss_acc.zero_()
@@ -1878,7 +1992,7 @@ class CTREngine:
         sp = self.spec
         acc = self.loss_acc.tolist()
         total = acc[0] + acc[1]
-        if getattr(self, "wide_lazy", False):
+        if getattr(self, "wide_flushes", False):
             self._wide_flush()
             total = (self.loss_acc[0] + self.loss_acc[1] + 0.5 * sp.l2 * self.wacc.sum()).item()
         return float(total), int(round(acc[2]))

@@ -16,6 +16,9 @@ at 1); with weight_key, evaluation's logloss and calibration are weighted too.
 cross_layers=N (dnn_pipeline, dnn_cate, dnn_multi, dnn_multi_cate) adds an N-layer Deep & Cross
 network on the tower input, its output joining the tower's in the output layer.
 
+wide_optimizer=ftrl wide_lr=0.05 wide_l1=1e-3 wide_l2=0 (wdl: models/wdl.py reads them from its args)
+train the wide weights with FTRL-proximal instead of Adam; L1 leaves most wide rows at exactly zero.
+
 Two more overrides choose what evaluation reports (deep_learning_amd/metrics.py); without them
 the output is the reference's: eval_metrics=auc,gauc,logloss,calibration (default auc) and
 gauc_slot=K, the cate_feats column whose id groups the samples for GAUC (the user-id slot).
@@ -78,6 +81,8 @@ class ModelParams:
                 self.weight_key = v
             elif k == "cross_layers":   # a cross network beside the dnn_* tower, stored only when given
                 self.cross_layers = check_cross_layers(v, self.alg_name)
+            elif k in ("wide_optimizer", "wide_lr", "wide_l1", "wide_l2"):   # stored only when given, too
+                setattr(self, k, check_wide_option(k, v, self.alg_name))
             else:
                 raise SystemExit("unknown override %s" % k)
         (self.cont_field_size, self.vector_feats_size, self.cate_field_size, self.multi_feats_size,
@@ -113,6 +118,25 @@ def check_cross_layers(v, alg_name):
         raise SystemExit("cross_layers=%s: the cross network joins the tower of %s only, not %s"
                          % (v, ", ".join(ModelSpec.CROSS_MODELS), alg_name))
     return n
+
+
+def check_wide_option(k, v, alg_name):
+    """wide_optimizer=adam|ftrl as a string, wide_lr / wide_l1 / wide_l2 as floats; refuses
+    (SystemExit) what ModelSpec would: another optimizer name, ftrl for a model other than wdl,
+    wide_lr <= 0, a negative wide_l1 / wide_l2, anything not finite."""
+    if k == "wide_optimizer":
+        if v not in ("adam", "ftrl"):
+            raise SystemExit("wide_optimizer=%s must be adam or ftrl" % v)
+        if v == "ftrl" and alg_name != "wdl":
+            raise SystemExit("wide_optimizer=ftrl: only wdl has wide weights, not %s" % alg_name)
+        return v
+    try:
+        x = float(v)
+    except ValueError:
+        raise SystemExit("%s=%s is not a number (wide_optimizer)" % (k, v))
+    if not (x == x and abs(x) != float("inf") and (x > 0.0 if k == "wide_lr" else x >= 0.0)):
+        raise SystemExit("%s=%s must be finite and %s 0 (wide_optimizer)" % (k, v, ">" if k == "wide_lr" else ">="))
+    return x
 
 
 def check_eval_options(eval_metrics, gauc_slot, cate_field_size):

@@ -224,7 +224,10 @@ class CTRModel:
 
 def _adam_state(eng):
     out = {"adam/opt": eng.opt.cpu().numpy(), "adam/steps": np.array([eng.steps])}
-    out.update({"adam/table_" + k: v for k, v in eng.adam_state().items()})
+    # (FTRL's z and n of the wide weights keep their own names: "ftrl/z", "ftrl/n")
+    out.update({k if k.startswith("ftrl/") else "adam/table_" + k: v for k, v in eng.adam_state().items()})
+    if eng.ftrl:   # the wide bias stays with Adam: its moments, for a bit-exact continuation
+        out["adam/wbm"], out["adam/wbv"] = eng.wbm.cpu().numpy(), eng.wbv.cpu().numpy()
     out["adam/hm"], out["adam/hv"] = eng.hm.cpu().numpy(), eng.hv.cpu().numpy()
     if eng.cross:   # the cross vector's moments, in the device layout (engine.py _cross_pack)
         out["adam/cm"], out["adam/cv"] = eng.cm.cpu().numpy(), eng.cv.cpu().numpy()
@@ -237,7 +240,12 @@ def _adam_state(eng):
 def _load_adam_state(eng, d):
     eng.set_opt(torch.from_numpy(d["adam/opt"]))
     eng.steps = int(d["adam/steps"][0])
-    eng.set_adam_state({k[len("adam/table_"):]: d[k] for k in d.files if k.startswith("adam/table_")})
+    st = {k[len("adam/table_"):]: d[k] for k in d.files if k.startswith("adam/table_")}
+    st.update({k: d[k] for k in d.files if k.startswith("ftrl/")})
+    eng.set_adam_state(st)   # (refuses a checkpoint of the other wide optimizer)
+    if eng.ftrl:
+        eng.wbm.copy_(torch.from_numpy(d["adam/wbm"]))
+        eng.wbv.copy_(torch.from_numpy(d["adam/wbv"]))
     eng.hm.copy_(torch.from_numpy(d["adam/hm"]))
     eng.hv.copy_(torch.from_numpy(d["adam/hv"]))
     if eng.cross:

@@ -9,7 +9,9 @@
 Math (engine, model "wdl"): xavier embedding table with no zero row, deep tower
 over [cont, V[cate]], cross logit sum_f w[wide_f] + sum_j w[Fw+j] h_j + b with the
 deep-output weights aliasing wide rows (wdl.py:225-253), eps-log-loss, L2 on
-wdl_weights and every hidden weight matrix (:269-275), TF1 Adam.  The deep tower
+wdl_weights and every hidden weight matrix (:269-275), TF1 Adam; with
+``args.wide_optimizer == "ftrl"`` wdl_weights is trained by FTRL-proximal instead
+(``wide_lr``, ``wide_l1``, ``wide_l2``).  The deep tower
 runs the fp32 MFMA GEMMs (the reference's numerics) unless ``args.tower_dtype == "bf16"``
 (BASELINE config C5: bf16 MFMA tower, fp32 master weights and fp32 wide cross logit).
 """
@@ -26,12 +28,15 @@ class DeepModel(LoadStyleModel):
         self.cate_index_size = int(args.cate_index_size)
         self.embedding_size = int(args.embedding_size)
         self.wide_feats_field_size = int(args.wide_field_size)
+        # wide_optimizer / wide_lr / wide_l1 / wide_l2 (local_run's overrides, present only when given)
+        wide_kw = {k: getattr(args, k) for k in ("wide_optimizer", "wide_lr", "wide_l1", "wide_l2")
+                   if getattr(args, k, None) is not None}
         return ModelSpec("wdl", C=self.cont_field_size, S=self.cate_field_size, E=self.embedding_size,
                          cate_index_size=self.cate_index_size, hidden=self.hidden_units,
                          Fw=self.wide_feats_field_size, lr=float(args.learning_rate), l2=float(args.l2_reg),
                          decay_steps=float(args.learning_rate_decay_steps),
                          decay_rate=float(args.learning_rate_decay_rate),
-                         tower=str(getattr(args, "tower_dtype", "f32")))
+                         tower=str(getattr(args, "tower_dtype", "f32")), **wide_kw)
 
     def native_fields(self):
         sp = self.spec

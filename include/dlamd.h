@@ -926,6 +926,32 @@ int dl_wide_rec_update(float* rec, const int32_t* n_uniq, int64_t max_uniq, cons
 int dl_wide_rec_flush(float* rec, int64_t w_rows, float l2, const float* hist, int32_t hist_len,
                       const float* opt, int64_t* sq_untouched, double* acc, void* stream);
 #define DL_LOSS_ACC_SLOTS 65536   /* slots of the wide running-loss accumulator (>= any grid above) */
+/* FTRL-proximal for the same wide weights (wide.hip; TF1 FtrlOptimizer(lr, learning_rate_power =
+ * -0.5, initial_accumulator_value = 0.1, l1, l2), ApplyFtrl / SparseApplyFtrl without shrinkage).
+ * Per touched row, g the exact fixed-point sum of the row's references:
+ *   n' = n + g^2;  z += g - (sqrt(n') - sqrt(n)) / lr * w;
+ *   w = |z| > l1 ? (sign(z) l1 - z) / (sqrt(n') / lr + 2 l2) : 0
+ * lr (finite, > 0), l1, l2 (finite, >= 0) are kernel scalars; lr is not decayed.  An untouched
+ * row keeps its bits: rec [w_rows][4] = {w, z, n, 0} carries no stamp, and there is no replay,
+ * no lag and no flush.  No atomics on the data path: the same inputs give the same bits.
+ * dl_wide_ftrl_gather: the deep-output rows Fw..Fw+H and the unique wide rows uniq_rows[u]
+ *   (u < min(n_uniq[0], max_uniq); n_uniq NULL: max_uniq) as they stand into wloc = [— (Fw) | deep
+ *   rows (H) | unique rows]; stash[u] = {w, z, n, row bits} when training (NULL: the predict
+ *   form).  A row outside [0, w_rows) raises DL_STATUS_INDEX (and poisons the step).
+ * dl_wide_ftrl_update: pass A, the step on the stashed unique rows from gloc[Fw + H + u] (+ the
+ *   deep term gloc[row] of a row in Fw..Fw+H, exact int64; dmark[row - Fw] set); pass B, the deep
+ *   rows dmark did not cover.  gloc and dmark are reset; a poisoned step writes no record.
+ * dl_ftrl_rows: the same step on the rows with touched[r] != 0 of the plane arrays w, z, n
+ *   ([rows] each; g_fixed the head's DL_WIDE_GRAD_SCALE gradient); g_fixed and touched of
+ *   those rows are reset, also by a poisoned step.  touched 4-B aligned. */
+int dl_wide_ftrl_gather(const float* rec, int64_t w_rows, const uint32_t* uniq_rows, const int32_t* n_uniq,
+                        int64_t max_uniq, int32_t Fw, int32_t H, const float* opt, float* wloc, float* stash,
+                        void* stream);
+int dl_wide_ftrl_update(float* rec, const int32_t* n_uniq, int64_t max_uniq, const float* stash, int64_t* gloc,
+                        int32_t Fw, int32_t H, float lr, float l1, float l2, const float* opt, uint8_t* dmark,
+                        void* stream);
+int dl_ftrl_rows(float* w, float* z, float* n, int64_t* g_fixed, uint8_t* touched, int64_t rows, float lr, float l1,
+                 float l2, const float* opt, void* stream);
 
 /* ------------------------------------------------------------------------
  * RCCL collectives of the row-sharded step (comm.cpp; SURVEY.md §8(b)3

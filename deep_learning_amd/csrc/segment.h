@@ -78,14 +78,14 @@ struct SegGradIn {
   const float* dx0;
   // multi-hot references (index_multi_base(L) <= slot; records only): nonzero-mean pooling
   // (deepfm_multi_cate.py:71-111) — slot ranges within the multi block and the per-sample
-  // pooled-slot gradients g_pool [B][n_slots][E], g1_pool [B][n_slots] (rec.hip pool_grad)
+  // pooled-slot gradients, one g_pitch-float row a (sample, slot): g_pool's E floats, g1_pool's
+  // entry at the same pitch (rec.hip pool_grad; dl_pool_desc)
   const int32_t* slot_start;
   const int32_t* slot_end;
   int n_slots;
   const float* g_pool;
   const float* g1_pool;
-  int g_pitch;    // floats between (sample, slot) rows of g_pool (E: packed)
-  int g1_stride;  // ... and between their g1_pool entries (1: packed; g_pitch: interleaved)
+  int g_pitch;    // floats between (sample, slot) rows of g_pool, and between their g1_pool entries
   // opt's status word: an index entry out of range (a corrupt batch index) sets
   // DL_STATUS_INDEX there and the host raises, instead of the entry being skipped silently
   int* status;
@@ -210,7 +210,7 @@ __device__ __forceinline__ SegGrad4 segment_grad4_range(const SegGradIn& a, int 
       const long long bmd = (DL_BWD_DIAG & 16) ? 0 : bm;
       const float4 gp = *reinterpret_cast<const float4*>(a.g_pool + bmd * a.g_pitch + 4 * q);
       r.x.x += gp.x; r.x.y += gp.y; r.x.z += gp.z; r.x.w += gp.w;
-      if (a.g1_pool) r.g1 += a.g1_pool[bmd * a.g1_stride];
+      if (a.g1_pool) r.g1 += a.g1_pool[bmd * a.g_pitch];
     } else if (L.use_fm && sl < S) {
       const float dzb = a.dz[b];
       const float4 fs = *reinterpret_cast<const float4*>(a.fm_sum + (long long)((DL_BWD_DIAG & 2) ? 0 : b) * E + 4 * q);
@@ -265,7 +265,7 @@ __device__ __forceinline__ SegRef seg_fetch(const SegGradIn& a, bool in, int k, 
     f.kind = 1;
     const long long bmd = (DL_BWD_DIAG & 16) ? 0 : bm;
     f.v = *reinterpret_cast<const float4*>(a.g_pool + bmd * a.g_pitch + 4 * q);
-    f.w = a.g1_pool ? a.g1_pool[bmd * a.g1_stride] : 0.f;
+    f.w = a.g1_pool ? a.g1_pool[bmd * a.g_pitch] : 0.f;
   } else if (L.use_fm && sl < S) {
     f.kind = 2;
     f.dzb = a.dz[b];

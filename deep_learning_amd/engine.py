@@ -333,9 +333,6 @@ class CTREngine:
             if gemm == "f32":
                 raise ValueError("dropout_keep_deep: not supported with gemm='f32' (the dropout epilogues are "
                                  "the s3 GEMMs')")
-            if os.environ.get("DLAMD_RELU_BITS", "1") == "0":
-                raise ValueError("dropout_keep_deep: not supported with DLAMD_RELU_BITS=0 (the dX GEMMs read the "
-                                 "keep bits from the forward's bitmask)")
             if type(self) is not CTREngine:
                 raise ValueError("dropout_keep_deep: not supported by %s (the mask is indexed by the local "
                                  "row number; a sharded batch needs global rows)" % type(self).__name__)
@@ -351,6 +348,13 @@ class CTREngine:
                              "row number; a sharded batch needs global rows)" % type(self).__name__)
         self.dev = torch.device(device)
         self.B = max_batch
+        # set later: predict's planes (flush(planes=True)) and the step they were written at,
+        # fused_gather_tab's offsets, the prefetch's side stream and buffer sets (_enable_slots)
+        self.p_plane = self.w1_plane = self.gtab = self.side = self._slots = None
+        self.planes_step = -1
+        self._cur = 0      # the buffer set in use
+        self._pfq = []     # pending prefetches, oldest first: (set, B, ready event, batch)
+        self._pf = None    # the oldest pending prefetch (_pfq[0])
         dev = self.dev
         z = lambda *s, dt=F32: torch.zeros(*s, dtype=dt, device=dev)
         E, S, M = sp.E, sp.S, sp.M
@@ -424,6 +428,7 @@ class CTREngine:
         # FTRL-proximal on wdl_weights (ModelSpec.wide_optimizer, wide.hip): wm / wv (the records'
         # second and third floats) hold FTRL's z and n; no flush, no wide L2 loss term
         self.ftrl = sp.wide_optimizer == "ftrl"
+        self.w_rows = 0
         if self.wdl:   # wdl_weights [N + H] (deep-output rows alias wide ids, wdl.py:241-248) + bias
             self.w_rows = N + sp.hidden[-1]
             wr = _ru(self.w_rows, 16)
@@ -436,9 +441,10 @@ class CTREngine:
         # with lazy-exact Adam (wide.hip): the batch's unique wide ids indexed, gathered caught
         # up into the head's compact local table [— (Fw) | deep-output rows | unique rows], and
         # only those rows (and the H deep-output rows) updated — in place of the dense L2 sweep
-        # over all N + H rows (wdl.py:270-271); bit-identical to it.  DLAMD_WIDE_LAZY=0: dense.
-        self.wide_lazy = bool(self.wdl and self.lazy and type(self) is CTREngine
-                              and os.environ.get("DLAMD_WIDE_LAZY", "1") != "0")
+        # over all N + H rows (wdl.py:270-271); bit-identical to it.  The table ids and the wide ids
+        # go through ONE index build (dl_index_build_pair): the table's index arrays hold both sets'
+        # sorted references and unique rows, the wide set's own arrays (widx_*) are split out of them
+        self.wide_lazy = self.wdl and self.lazy and type(self) is CTREngine
         self.wide_flushes = self.wide_lazy and not self.ftrl   # Adam's records lag and need catching up
         if self.wide_lazy:
             Fw, Hh, Bm = sp.Fw, sp.hidden[-1], max_batch
@@ -458,9 +464,7 @@ class CTREngine:
             self.wacc = z(_lib.LOSS_ACC_SLOTS, dt=torch.float64)
             self.wrep = z(max(nw, 1))
             self.in_wide_loc = z(Bm, Fw, dt=torch.int64)
-            wsb = _lib.lib().dl_index_workspace_bytes(max(1, nw))
-            self.widx_ws = z(wsb, dt=torch.uint8)
-            self.widx_keys, self.widx_refs, self.widx_uniq = (z(max(nw, 1), dt=torch.int32) for _ in range(3))
+            self.widx_refs, self.widx_uniq = (z(max(nw, 1), dt=torch.int32) for _ in range(2))
             self.widx_off = z(nw + 1, dt=torch.int32)
             self.widx_n = z(4, dt=torch.int32)
             self.winv = z(max(nw, 1), dt=torch.int32)
@@ -503,11 +507,9 @@ class CTREngine:
             self.h.append(t)
         self.dh = [z(B, self.h_ld[l]) for l in range(len(sp.hidden))]
         # the forward's ReLU sign bitmasks (s3 tower; dl_gemm_s3_nt_bits): the dX ReluGrad
-        # epilogue reads 2 bytes per 16 columns instead of the f32 activations.
-        # DLAMD_RELU_BITS=0 keeps the f32 mask.
-        self.relu_bits = bool(self.s3 and os.environ.get("DLAMD_RELU_BITS", "1") != "0")
+        # epilogue reads 2 bytes per 16 columns instead of the f32 activations
         self.hbits_ld = [_ru(-(-h // 16), 32) for h in sp.hidden]
-        self.hbits = [z(B, self.hbits_ld[l], dt=torch.int16) for l in range(len(sp.hidden) - 1)] if self.relu_bits else []
+        self.hbits = [z(B, self.hbits_ld[l], dt=torch.int16) for l in range(len(sp.hidden) - 1)] if self.s3 else []
         self.bf = sp.tower == "bf16"
         # bf16 tower without pooled fields: the embedding forward writes the bf16 x0 itself
         self.x0_direct = self.bf and not sp.M
@@ -579,9 +581,9 @@ class CTREngine:
                 # per (sample, slot): the slot gradient (E floats) and the first-order one at
                 # column E of a row padded to whole 128-B lines (one line fetch per multi-hot
                 # reference in the backward instead of two: dl_pool_desc.g_pitch)
-                gp = 0 if os.environ.get("DLAMD_GPOOL_PACKED") else _ru(E + 1, 32)   # env: A/B only
-                self.g_pool = z(B, M, gp or E)
-                self.g1_pool = self.g_pool.view(-1)[E:] if gp else z(B, M)
+                gp = _ru(E + 1, 32)
+                self.g_pool = z(B, M, gp)
+                self.g1_pool = self.g_pool.view(-1)[E:]
                 self.pool_desc = _lib.PoolDesc(
                     slot_start=self.slot_start.data_ptr(), slot_end=self.slot_end.data_ptr(), n_slots=M,
                     fm_col=self.fm_pool_col, dx0_pool_col=S * E, g_pitch=gp, x0=self.x0.data_ptr(),
@@ -591,13 +593,8 @@ class CTREngine:
         self.bwd = bwd
         self.n_slot = (S if sp.fm else 0) + S + (sp.multi_width if self.lazy else 0)
         self.n_refs = B * self.n_slot
-        # wide_lazy: the table ids and the wide ids in ONE index build (dl_index_build_pair): the
-        # table's index arrays hold both sets' sorted references and unique rows, the wide set's
-        # own arrays (widx_*) are split out of them.  DLAMD_INDEX_PAIR=0: two builds.
-        self.index_pair = bool(getattr(self, "wide_lazy", False) and bwd == "sorted"
-                               and os.environ.get("DLAMD_INDEX_PAIR", "1") != "0")
         if bwd == "sorted":
-            cap = self.n_refs + (B * sp.Fw if self.index_pair else 0)
+            cap = self.n_refs + (B * sp.Fw if self.wide_lazy else 0)   # the pair build's wide references
             wsb = _lib.lib().dl_index_workspace_bytes(max(1, cap))
             self.idx_ws = z(wsb, dt=torch.uint8)
             self.idx_keys = z(cap, dt=torch.int32)
@@ -606,9 +603,6 @@ class CTREngine:
             self.idx_off = z(cap + 1, dt=torch.int32)
             self.idx_n = z(4, dt=torch.int32)
             self.idx_inv = z(cap, dt=torch.int32) if self.lazy else None
-            if self.index_pair:   # the second build's workspace and key array are not needed
-                self.widx_ws = z(256, dt=torch.uint8)
-                self.widx_keys = z(1, dt=torch.int32)
         if self.lazy:
             self.rows_u = z(self.n_rep + self.n_refs, E)
             self.rows_u1 = z(self.n_rep + self.n_refs)
@@ -627,7 +621,7 @@ class CTREngine:
             # the batch's weights, its effective weights and {inv_norm, N_nz} (dl_weight_norm, in _pre):
             # per buffer set, as the labels they belong to
             self.in_weight, self.w_eff, self.norm = z(B), z(B), z(4)
-        self.graphs = {}        # (buffer set, batch) -> captured step
+        self.graphs = {}        # (buffer set, batch, not indexed) -> captured step; (set, batch, "pre") -> index build
         # predict on a flushed table reads dense p / first-order planes written by the flush
         # (DLAMD_FLAT_PLANES=0: each reference reads its record's first line instead)
         self.flat_planes = os.environ.get("DLAMD_FLAT_PLANES", "1") != "0"
@@ -719,7 +713,7 @@ class CTREngine:
             v = rng.standard_normal((2 * Lc + 1, D)) * math.sqrt(2.0 / (D + D))
             v[0] = rng.standard_normal(D) * math.sqrt(2.0 / (D + H + 1))
             self.cw[: self.cross_n].copy_(torch.from_numpy(v.astype(np.float32).reshape(-1)))
-        if getattr(self, "wide_lazy", False):
+        if self.wide_lazy:
             self._wide_pack()
         torch.cuda.synchronize()
 
@@ -737,7 +731,7 @@ class CTREngine:
     def _refresh_wb(self, l, s=None):
         """The tower's operand copies of the fp32 master weights W_l: bf16 tower, bf16 W and
         W^T; split (s3) GEMMs, the three bf16 planes of W and of W^T."""
-        if getattr(self, "s3", False):
+        if self.s3:
             s = s if s is not None else _lib.stream_handle()
             i, o = self.in_ld[l], self.out_ld[l]
             call("dl_split3", ptr(self.W[l]), i, o, o, 0, ptr(self.Wp[l]), o, i * o, s)
@@ -925,7 +919,7 @@ class CTREngine:
 
     def _wide_state(self):
         """(w, m, v) of wdl_weights as device tensors (records: caught up first), or Nones."""
-        if not getattr(self, "wdl", False):
+        if not self.wdl:
             return None, None, None
         if not self.wide_lazy:
             return self.ww, self.wm, self.wv
@@ -995,7 +989,7 @@ class CTREngine:
             return
         pp = w1 = None
         flags = self.rec_flags
-        if planes and getattr(self, "p_plane", None) is None:
+        if planes and self.p_plane is None:
             # FM models: one slot plane, rows x 2E f32 (p, then the first-order weight in column E:
             # an FM reference's row and weight in one 128-B slot, one random request instead of
             # two — 3.3 GB at 26 M rows, E = 16); otherwise a rows x E p plane (1.7 GB).  Dropped
@@ -1016,8 +1010,9 @@ class CTREngine:
         self._c("rec_flush", "dl_rec_flush", ptr(self.rec), self.rec_ld, self.spec.E, flags,
                 self.rec.shape[0], ptr(self.hist), self.hist_len, ptr(self.opt), ptr(pp), ptr(w1),
                 _lib.stream_handle())
-        self.planes_step = self.steps if planes else getattr(self, "planes_step", -1)
-        if getattr(self, "wide_flushes", False):
+        if planes:
+            self.planes_step = self.steps
+        if self.wide_flushes:
             self._wide_flush()
         self.since_flush = 0
 
@@ -1075,7 +1070,7 @@ class CTREngine:
         if _lib.lib().dl_embed_fwd_gtab_ok(C_ref(self._flat_layout(B))) != 1:
             return False
         n = -(-B // 256) * sp.S * 272
-        if getattr(self, "gtab", None) is None or self.gtab.numel() < n:
+        if self.gtab is None or self.gtab.numel() < n:
             self.gtab = torch.empty(n, dtype=torch.int32, device=self.dev)
         return True
 
@@ -1091,7 +1086,7 @@ class CTREngine:
             return False
         if self.cross:   # the cross network reads x0's deep columns, which the fused forms leave unwritten
             return False
-        pl = getattr(self, "p_plane", None)
+        pl = self.p_plane
         return (pl is not None and self.cat_col == 0 and sp.E in (8, 16, 32, 64) and 0 < sp.S <= 40
                 and (sp.S * sp.E) % 32 == 0 and sp.S * sp.E <= self.in_ld[0]
                 and pl.shape[0] * pl.shape[1] * 4 < 0xFFFFFF00)
@@ -1241,7 +1236,7 @@ class CTREngine:
                  ptr(self.in_cate), sp.S, ptr(self.slot_start), ptr(self.slot_end), sp.M, self.fm_pool_col,
                  ptr(self.x0), ptr(self.fm_out), ptr(self.cnt_emb), ptr(self.cnt_first), ptr(self.err), s)
         if (not train and self.lazy and not sp.M and self.since_flush == 0 and type(self) is CTREngine
-                and getattr(self, "planes_step", -1) == self.steps):
+                and self.planes_step == self.steps):
             # predict on a flushed table whose planes are current (flush(planes=True) at this
             # step): the plain lookup of the dense layout (dl_embed_fwd_slots / dl_embed_fwd),
             # its deep rows read by the first tower layer itself where it can (fused_gather_l0)
@@ -1426,13 +1421,14 @@ class CTREngine:
         cate = self.in_cate if self.bwd != "sorted" else None
         wide = self.in_wide if self.wdl else None
         self._c("validate", "dl_validate_batch", C_ref(L), ptr(cate), ptr(wide), sp.Fw if wide is not None else 0,
-                self.in_wide.shape[1], getattr(self, "w_rows", 0), 1, ptr(self.err), s)
+                self.in_wide.shape[1], self.w_rows, 1, ptr(self.err), s)
         if self.weighted and weights:
             self._c("weight_norm", "dl_weight_norm", ptr(self.in_weight), ptr(self.in_label), B, sp.pos_weight,
                     ptr(self.w_eff), ptr(self.norm), ptr(self.err), s)
         if self.bwd != "sorted":
             return
-        if self.index_pair:
+        if self.wide_lazy:
+            # the table ids and the wide ids in one build, then the head's local wide ids
             WL = self.wlayout
             WL.batch = B
             self._c("index_build", "dl_index_build_pair", C_ref(L), ptr(self.in_cate), C_ref(WL), ptr(self.in_wide),
@@ -1447,40 +1443,13 @@ class CTREngine:
                 self.idx_ws.numel(), ptr(self.idx_keys), ptr(self.idx_refs), ptr(self.idx_uniq),
                 ptr(self.idx_off), ptr(self.idx_n), ptr(self.idx_inv) if self.lazy else None, None,
                 ptr(self.err), s)
-        if getattr(self, "wide_lazy", False):
-            # the wide ids' index (unique wdl_weights rows, inverse map) and the head's local ids
-            WL = self.wlayout
-            WL.batch = B
-            Fw, H = sp.Fw, sp.hidden[-1]
-            self._c("index_build_wide", "dl_index_build", C_ref(WL), ptr(self.in_wide), 1, 0, ptr(self.widx_ws),
-                    self.widx_ws.numel(), ptr(self.widx_keys), ptr(self.widx_refs), ptr(self.widx_uniq),
-                    ptr(self.widx_off), ptr(self.widx_n), ptr(self.winv), None, ptr(self.err), s)
-            call("dl_wide_local_ids", ptr(self.winv), B * Fw, Fw + H, ptr(self.in_wide_loc), s)
 
-    def _train(self, B, part="all"):
-        """The step's launches; part "front" = through the tower's backward and dense Adam,
-        "back" = the embedding backward onwards (train_step's DLAMD_PF_MID split)."""
-        self._train_body(B, part)
-        if part == "front":
-            return
-        # the step's loss into the running sum (read once per epoch: loss_sum_end)
-        sp = self.spec
-        width = self.head_slab.shape[1]
-        coef = sp.l2 if sp.hidden_reg == "l1" else 0.5 * sp.l2
-        if self.weighted:
-            self._c("loss_acc", "dl_loss_accumulate_weighted", ptr(self.head_slab), call_int(self.head_grid, B), width,
-                    width - 1, ptr(self.norm), ptr(self.opt), coef, ptr(self.loss_acc), ptr(self._ring),
-                    _lib.stream_handle())
-            return
-        self._c("loss_acc", "dl_loss_accumulate", ptr(self.head_slab), call_int(self.head_grid, B), width, width - 1,
-                1.0 / B, ptr(self.opt), coef, ptr(self.loss_acc), ptr(self._ring), _lib.stream_handle())
-
-    def _train_body(self, B, part="all"):
+    def _train(self, B):
+        """The step's launches: forward, the tower's backward and dense Adam, the embedding
+        backward and the remaining updates (_train_back), the step's loss into the running sum."""
         sp = self.spec
         s = _lib.stream_handle()
         L = self.layout
-        if part == "back":
-            return self._train_back(B, s, L)
         # a batch whose ids failed validation (index build) poisons the step: nothing is applied
         # (dl_step_begin: the guard, the Adam step begin and the lazy tables' alpha ring entry)
         self._c("step_begin", "dl_step_begin", ptr(self.err), ptr(self.opt), sp.decay_rate, float(sp.decay_steps),
@@ -1520,8 +1489,16 @@ class CTREngine:
             self._c("cross_bwd", "dl_cross_bwd", B, self.D0, self.cross, ptr(self.x0), self.in_ld[0], ptr(self.cw),
                     ptr(self.cross_s), ptr(self.dz), ptr(self.dx0), self.dx_ld, self.cat_col, self.dx_cols,
                     ptr(self.cross_slab), self.cross_blocks, s)
-        if part == "all":
-            self._train_back(B, s, L)
+        self._train_back(B, s, L)
+        # the step's loss into the running sum (read once per epoch: loss_sum_end)
+        width = self.head_slab.shape[1]
+        coef = sp.l2 if sp.hidden_reg == "l1" else 0.5 * sp.l2
+        if self.weighted:
+            self._c("loss_acc", "dl_loss_accumulate_weighted", ptr(self.head_slab), call_int(self.head_grid, B), width,
+                    width - 1, ptr(self.norm), ptr(self.opt), coef, ptr(self.loss_acc), ptr(self._ring), s)
+            return
+        self._c("loss_acc", "dl_loss_accumulate", ptr(self.head_slab), call_int(self.head_grid, B), width, width - 1,
+                1.0 / B, ptr(self.opt), coef, ptr(self.loss_acc), ptr(self._ring), s)
 
     def _cast_dh(self, B, s):
         """The bf16 tower's copy of the head's dh[-1] (the wdl head writes its bf16 dY itself)."""
@@ -1572,14 +1549,10 @@ class CTREngine:
                 self._c("gemm_dx_l%d" % l, "dl_gemm_s3_nt_drop", B, sp.hidden[l - 1], o, ptr(self.dh[l]),
                         self.h_ld[l], ptr(self.Wp[l]), o, i * o, ptr(self.dh[l - 1]), self.h_ld[l - 1], 3,
                         None, 0, ptr(self.hbits[l - 1]), self.hbits_ld[l - 1], *self._drop_args(l), s)
-            elif l > 0 and self.relu_bits:   # ReluGrad from the forward's sign bitmask
+            elif l > 0:   # ReluGrad from the forward's sign bitmask
                 self._c("gemm_dx_l%d" % l, "dl_gemm_s3_nt_bits", B, sp.hidden[l - 1], o, ptr(self.dh[l]),
                         self.h_ld[l], ptr(self.Wp[l]), o, i * o, ptr(self.dh[l - 1]), self.h_ld[l - 1], 3,
                         None, 0, ptr(self.hbits[l - 1]), self.hbits_ld[l - 1], s)
-            elif l > 0:
-                self._c("gemm_dx_l%d" % l, "dl_gemm_s3_nt", B, sp.hidden[l - 1], o, ptr(self.dh[l]),
-                        self.h_ld[l], ptr(self.Wp[l]), o, i * o, ptr(self.dh[l - 1]), self.h_ld[l - 1], 2,
-                        ptr(self.h[l - 1]), self.h_ld[l - 1], s)
             else:
                 self._c("gemm_dx_l0", "dl_gemm_s3_nt", B, self.dx_cols, o, ptr(self.dh[0]), self.h_ld[0],
                         ptr(self.Wp[0]), o, i * o, ptr(self.dx0), self.dx_ld, 0, None, 0, s)
@@ -1627,6 +1600,7 @@ class CTREngine:
                 and os.environ.get("DLAMD_ADAM_FUSED", "1") != "0")
 
     def _train_back(self, B, s, L):
+        """_train from the embedding backward onwards: the table, head / wide and cross updates."""
         sp = self.spec
         # embedding backward (uses pre-update table and head weights)
         bwd_blocks = call_int("dl_embed_bwd_grid", C_ref(L))
@@ -1718,14 +1692,14 @@ class CTREngine:
     # buffered — the next batch is staged and indexed into the other set on a side stream
     # while the current step runs.
     SLOT_ATTRS = ("in_label", "in_cont", "in_vec", "in_cate", "in_wide", "idx_ws", "idx_keys", "idx_refs",
-                  "idx_uniq", "idx_off", "idx_n", "idx_inv", "err", "widx_ws", "widx_keys", "widx_refs", "widx_uniq",
+                  "idx_uniq", "idx_off", "idx_n", "idx_inv", "err", "widx_refs", "widx_uniq",
                   "widx_off", "widx_n", "winv", "in_wide_loc", "in_weight", "w_eff", "norm")
 
     def _side_stream(self):
-        if getattr(self, "side", None) is None:
+        if self.side is None:
             # high priority: a hardware queue of its own (a default-priority stream can share
             # the compute stream's queue, which serialises the two)
-            self.side = torch.cuda.Stream(priority=int(os.environ.get("DLAMD_SIDE_PRIORITY", "-1")))
+            self.side = torch.cuda.Stream(priority=-1)
         return self.side
 
     def _use_slot(self, k):
@@ -1734,23 +1708,18 @@ class CTREngine:
         self._cur = k
 
     def _enable_slots(self):
-        if getattr(self, "_slots", None) is not None:
+        if self._slots is not None:
             return
         a = {n: getattr(self, n) for n in self.SLOT_ATTRS if getattr(self, n, None) is not None}
-        depth = max(1, getattr(self, "pf_depth", 1))
+        depth = max(1, self.pf_depth)
         self._slots = [a] + [{n: torch.zeros_like(t) for n, t in a.items()} for _ in range(depth)]
-        self._cur = 0
         self._slot_free = [None] * len(self._slots)   # event: the compute stream is done with a set
-        self._pfq = []                    # pending prefetches, oldest first: (set, B, ready event, batch)
-        self._pf = None                   # the oldest pending prefetch (_pfq[0])
 
-    def prefetch(self, batch, graph=False, after=None):
+    def prefetch(self, batch, graph=False):
         """Stage `batch` and build its index into an idle buffer set on the side stream;
         train_step(batch) then starts from it.  Up to pf_depth batches may be pending (buffer
         sets: pf_depth + 1), consumed in order.  graph=True replays the index build as a
-        captured hipGraph (one per buffer set and batch size).  after: an event on the compute
-        stream recorded after every earlier step; the side stream starts from it (instead of
-        from the moment the chosen buffer set is free)."""
+        captured hipGraph (one per buffer set and batch size)."""
         self._enable_slots()
         if any(p[3] is batch for p in self._pfq) or len(self._pfq) >= len(self._slots) - 1:
             return
@@ -1758,9 +1727,7 @@ class CTREngine:
         used = {cur} | {p[0] for p in self._pfq}
         k = next(i for i in range(len(self._slots)) if i not in used)
         side = self._side_stream()
-        if after is not None:
-            side.wait_event(after)
-        elif self._slot_free[k] is not None:
+        if self._slot_free[k] is not None:
             side.wait_event(self._slot_free[k])
         else:
             side.wait_stream(torch.cuda.current_stream())
@@ -1787,7 +1754,7 @@ class CTREngine:
         """Buffers of this step's batch: the prefetched set if `batch` is the oldest one
         prefetched, else (every pending prefetch dropped once it lands) staged and indexed now
         on the compute stream."""
-        q = getattr(self, "_pfq", None) or []
+        q = self._pfq
         if q and batch is not None and batch is q[0][3]:
             k, B, ev, _ = q.pop(0)
             self._pf = q[0] if q else None
@@ -1812,7 +1779,7 @@ class CTREngine:
 
     def _release(self):
         """Mark the current buffer set free once the compute stream's queued work is done."""
-        if getattr(self, "_slots", None) is not None:
+        if self._slots is not None:
             ev = torch.cuda.Event()
             ev.record()
             self._slot_free[self._cur] = ev
@@ -1821,7 +1788,7 @@ class CTREngine:
         """One training step on `batch` (or on the already-staged slots if None).
         next_batch: prefetch it (stage + index build on the side stream) during this step."""
         B, indexed = self._begin(batch)
-        if getattr(self, "p_plane", None) is not None:   # predict's planes go stale: free them
+        if self.p_plane is not None:   # predict's planes go stale: free them
             self.p_plane = self.w1_plane = None
             self.planes_step = -1
         if self.lazy:
@@ -1832,43 +1799,14 @@ class CTREngine:
         if not indexed and not graph:
             self._pre(B)
         # next_batch: the batch after this one, or a list of the next ones (up to pf_depth are
-        # kept in flight); prefetched before this step's graph is submitted, or after it
-        # (DLAMD_PF_AFTER=1)
+        # kept in flight), prefetched before this step's graph is submitted
         ahead = [] if next_batch is None else list(next_batch) if isinstance(next_batch, (list, tuple)) else [next_batch]
-        pf_after = os.environ.get("DLAMD_PF_AFTER", "0") == "1"
-        pf_graph = graph and os.environ.get("DLAMD_PF_EAGER", "0") != "1"
-        # DLAMD_PF_MID=1: the step in two launches, the prefetch's staging and index build
-        # released between them — beside the embedding backward, not the tower GEMMs
-        pf_mid = bool(ahead) and not pf_after and os.environ.get("DLAMD_PF_MID", "0") == "1"
-        if pf_mid:
-            self._step_mark(0)
-            for part in ("front", "back"):
-                if graph:
-                    key = (getattr(self, "_cur", 0), B, not indexed, part)
-                    g = self.graphs.get(key)
-                    if g is None:
-                        g = self.graphs[key] = self._capture(B, with_pre=not indexed, part=part)
-                    g.replay()
-                else:
-                    self._train(B, part)
-                if part == "front":
-                    mid = torch.cuda.Event()
-                    mid.record()
-                    for nb in ahead:
-                        self.prefetch(nb, graph=pf_graph, after=mid)
-            self._step_mark(1)
-            self._release()
-            self._queue_status()
-            self.steps += 1
-            self.last_batch = B
-            return B
-        if not pf_after:
-            for nb in ahead:
-                self.prefetch(nb, graph=pf_graph)
+        for nb in ahead:
+            self.prefetch(nb, graph=graph)
         self._step_mark(0)
         if graph:
             # one graph per (buffer set, batch size, index built inside or prefetched)
-            key = (getattr(self, "_cur", 0), B, not indexed)
+            key = (self._cur, B, not indexed)
             g = self.graphs.get(key)
             if g is None:
                 g = self.graphs[key] = self._capture(B, with_pre=not indexed)
@@ -1877,9 +1815,6 @@ class CTREngine:
             self._train(B)
         self._step_mark(1)
         self._release()
-        if pf_after:
-            for nb in ahead:
-                self.prefetch(nb, graph=pf_graph)
         self._queue_status()
         self.steps += 1
         self.last_batch = B
@@ -1916,18 +1851,17 @@ class CTREngine:
         spw = 64 // (self.spec.E // 4)
         return max(1, min(bwd_blocks, (B + 16 * spw - 1) // (16 * spw)))
 
-    def _capture(self, B, with_pre=False, pre_only=False, part="all"):
+    def _capture(self, B, with_pre=False, pre_only=False):
         """Capture the step (with its index build when `with_pre`), or only the index build
-        (`pre_only`: the prefetch graph), on a capture stream; replayed on the caller's.
-        part: the whole step, or its front / back half (see _train)."""
+        (`pre_only`: the prefetch graph), on a capture stream; replayed on the caller's."""
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         g = torch.cuda.CUDAGraph()
         with capture_guard(), torch.cuda.graph(g, stream=s, capture_error_mode="thread_local"):
-            if (with_pre and part != "back") or pre_only:
+            if with_pre or pre_only:
                 self._pre(B)
             if not pre_only:
-                self._train(B, part)
+                self._train(B)
         torch.cuda.current_stream().wait_stream(s)
         return g
 
@@ -1937,7 +1871,7 @@ class CTREngine:
         the last flush) the first predict writes the p / first-order planes once (a flush
         that only copies: every row is caught up) and every later one reads them."""
         if (self.lazy and not self.spec.M and self.since_flush == 0 and type(self) is CTREngine
-                and getattr(self, "planes_step", -1) != self.steps and self.flat_planes):
+                and self.planes_step != self.steps and self.flat_planes):
             self.flush(planes=True)
         B, indexed = self._begin(batch)
         s = _lib.stream_handle()
@@ -1966,7 +1900,7 @@ class CTREngine:
         if sp.hidden_reg == "l1":   # l1_regularizer: scale * sum |W| (dnn.py:88-90)
             return data + sp.l2 * _lib.reg_sum(self.opt)
         reg = _lib.reg_sum(self.opt)
-        if getattr(self, "wide_flushes", False):
+        if self.wide_flushes:
             # the wide rows the step left untouched: their L2 term from a flush (wide.hip); the
             # touched rows' from the update's block partials — only the blocks this batch size
             # launched (a smaller last batch leaves an earlier batch's partials beyond them)
@@ -1981,7 +1915,7 @@ class CTREngine:
         regulariser terms on the device (dl_loss_accumulate), and with lazy wide records their
         L2 term arrives as the records are applied (the wide table is flushed first, so every
         replayed step from here on belongs to the sum)."""
-        if getattr(self, "wide_flushes", False):
+        if self.wide_flushes:
             self._wide_flush()
             self.wacc.zero_()
         self.loss_acc.zero_()
@@ -1992,7 +1926,7 @@ class CTREngine:
         sp = self.spec
         acc = self.loss_acc.tolist()
         total = acc[0] + acc[1]
-        if getattr(self, "wide_flushes", False):
+        if self.wide_flushes:
             self._wide_flush()
             total = (self.loss_acc[0] + self.loss_acc[1] + 0.5 * sp.l2 * self.wacc.sum()).item()
         return float(total), int(round(acc[2]))
@@ -2005,9 +1939,6 @@ class CTREngine:
         in the failing sess.run; here the failing step itself has applied nothing)."""
         if self._ring is not None:
             return self._ring_status()
-        every = int(os.environ.get("DLAMD_STATUS_EVERY", "1"))   # A/B: read back every N steps
-        if every > 1 and self.steps % every:
-            return
         if self._status_host is None:
             self._status_host = torch.zeros(4, dtype=torch.int32, pin_memory=True)
         k = self.steps % 4
@@ -2075,7 +2006,7 @@ class CTREngine:
 
     def _error_words(self):
         words = [self.err]
-        for sl in (getattr(self, "_slots", None) or []):
+        for sl in self._slots or []:
             if sl.get("err") is not None and sl["err"] is not self.err:
                 words.append(sl["err"])
         return words

@@ -196,7 +196,6 @@ class ShardedCTREngine(CTREngine):
         z = lambda *sh, dt=torch.float32: torch.zeros(*sh, dtype=dt, device=self.dev)
         E, W = spec.E, self.world
         self.local_rows = local_rows
-        self.side = None
         self.host_marks = [] if os.environ.get("DLAMD_HOST_TIMING") else None
         self.slack = float(os.environ.get("DLAMD_SHARD_SLACK", self.SLACK)) if slack is None else float(slack)
         self.lag = int(lag)
@@ -298,7 +297,7 @@ class ShardedCTREngine(CTREngine):
             per_batch.update({"wids_all": z(nb * wcap, dt=torch.int32), "whdr_all": z(nb * 4, dt=torch.int32)})
         for k, t in per_batch.items():
             setattr(self, k, t)
-        if getattr(self, "_slots", None) is not None:
+        if self._slots is not None:
             for sl in self._slots:
                 for k, t in per_batch.items():
                     sl[k] = torch.zeros_like(t)
@@ -866,9 +865,9 @@ class ShardedCTREngine(CTREngine):
         return g
 
     # ------------------------------------------------------------ step
-    def prefetch(self, batch, graph=False, after=None):
+    def prefetch(self, batch, graph=False):
         """Stage the next batch, index and route it on the side stream while this step runs."""
-        super().prefetch(batch, graph=False, after=after)
+        super().prefetch(batch, graph=False)
 
     def train_step(self, batch=None, graph=False, next_batch=None):
         """One training step on this rank's batch (every rank calls it together).  Returns B.
@@ -896,7 +895,7 @@ class ShardedCTREngine(CTREngine):
         # the first steps run eagerly: RCCL connects its peers then, not inside a capture
         if (graph and self.prof is None and self._steps_eager >= 1 and not self.exch.staged
                 and os.environ.get("DLAMD_SHARD_GRAPH", "1") != "0" and not getattr(self, "_graph_failed", False)):
-            key = (getattr(self, "_cur", 0), B)
+            key = (self._cur, B)
             g = self.graphs.get(key)
             if g is None:
                 try:
@@ -1017,7 +1016,7 @@ class ShardedCTREngine(CTREngine):
         must call it together.  Returns the sigmoid scores [B] (or logits) as host numpy, or a
         device tensor copy with device=True."""
         self._check_reports(0)
-        q = getattr(self, "_pfq", None) or []
+        q = self._pfq
         for p in q:   # pending prefetches: let them land, drop them
             torch.cuda.current_stream().wait_event(p[2])
         if q:

@@ -755,11 +755,10 @@ int dl_rec_gather(const dl_emb_layout* L, const float* rec, int32_t rec_ld, int3
 /* Multi-hot pooling state for dl_rec_bwd_adam (deepfm_multi_cate.py:71-111): slot ranges
  * within the multi block, the head column of the pooled first-order outputs, dx0's pooled
  * columns, the pooled x0 (L->x0_pool_col), the nonzero counts of dl_pool_fwd_indexed and
- * scratch g_pool [B][n_slots][E], g1_pool [B][n_slots] for the per-slot gradients.
- * g_pitch > 0 (>= E + 1, a multiple of 4): row (b, m) of g_pool at g_pool + (b*n_slots + m)*g_pitch
- * and its first-order gradient at g1_pool[(b*n_slots + m)*g_pitch] — with g1_pool = g_pool + E
- * and g_pitch = 32 (E = 16) both sit in one 128-B line, so a multi-hot reference's gradient
- * costs one line fetch instead of two; g_pitch = 0: the packed layouts above. */
+ * the per-slot gradients' scratch, [B][n_slots] rows of g_pitch floats (>= E + 1, a multiple of
+ * 4): row (b, m) of g_pool at g_pool + (b*n_slots + m)*g_pitch and its first-order gradient at
+ * g1_pool[(b*n_slots + m)*g_pitch] — with g1_pool = g_pool + E and g_pitch = 32 (E = 16) both
+ * sit in one 128-B line, so a multi-hot reference's gradient costs one line fetch, not two. */
 typedef struct dl_pool_desc {
   const int32_t* slot_start;
   const int32_t* slot_end;

@@ -1,5 +1,5 @@
-"""The backward's HBM bytes split by access stream (scripts/gpu_r4.sh bwddiag): FETCH_SIZE /
-WRITE_SIZE of rec_bwd_adam for the default build and the DL_BWD_DIAG builds that redirect one
+"""The backward's HBM bytes split by access stream (the counter runs recorded in profiles/r04g/;
+the script that made them is retired): FETCH_SIZE / WRITE_SIZE of rec_bwd_adam for the default build and the DL_BWD_DIAG builds that redirect one
 stream to a cache-resident address (d1: the dx0 slices, d2: the fm_sum rows, d8: no record
 writes).  Each stream's raw FETCH_SIZE delta is reported with the gfx950 x2 correction
 (MI355X_MICROARCH.md: coalesced streaming reads are tallied at half their bytes) and without:

@@ -62,3 +62,15 @@ def test_reader_header_symbols_exported():
     exported = {l.split()[-1] for l in out.splitlines() if " T dlio_" in l}
     assert len(declared) == 9 and declared == exported == set(nr.SIGNATURES)
     nr.lib()
+
+
+def test_design_table_lists_the_environment_names_the_package_reads():
+    """DESIGN.md §8c's table and the package name the same DLAMD_* switches (text only)."""
+    import glob
+    used = set()
+    for f in glob.glob(os.path.join(ROOT, "deep_learning_amd", "**", "*.py"), recursive=True):
+        used |= set(re.findall(r"DLAMD_[A-Z0-9_]+", open(f).read()))
+    design = open(os.path.join(ROOT, "DESIGN.md")).read()
+    sec = design.split("## 8c.", 1)[1].split("\n## ", 1)[0]
+    listed = set(re.findall(r"DLAMD_[A-Z0-9_]+", "\n".join(l for l in sec.splitlines() if l.startswith("| `DLAMD_"))))
+    assert listed and used == listed, "table only: %s; package only: %s" % (sorted(listed - used), sorted(used - listed))

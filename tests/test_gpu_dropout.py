@@ -356,7 +356,7 @@ def test_wdl_lazy_wide_equals_dense_with_dropout(hip_lib):
     assert not np.array_equal(_train(plain, bs[:1], graph=False)[0], zd[0])
 
 
-def test_refused_combinations(hip_lib, monkeypatch):
+def test_refused_combinations(hip_lib):
     keeps = {"dropout_keep_deep": KEEPS}
     with pytest.raises(ValueError, match="bf16"):
         CTREngine(ModelSpec("dnn_cate", tower="bf16", **KW, **keeps), max_batch=64)
@@ -370,8 +370,5 @@ def test_refused_combinations(hip_lib, monkeypatch):
     mk = dict(V=4, S=8, E=16, cate_index_size=6000, hidden=[48, 32], multi_ranges=[[0, 30, "a"], [30, 50, "b"]])
     with pytest.raises(ValueError, match="multi-hot"):
         CTREngine(ModelSpec("deepfm_multi_cate", dropout_keep_deep=(0.9, 0.8, 0.8), **mk), max_batch=64)
-    monkeypatch.setenv("DLAMD_RELU_BITS", "0")
-    with pytest.raises(ValueError, match="DLAMD_RELU_BITS"):
-        CTREngine(ModelSpec("dnn_cate", **KW, **keeps), max_batch=64)
     # no dropout: every one of them still builds
     CTREngine(ModelSpec("dnn_cate", dropout_keep_deep=[1, 1, 1, 1], **KW), max_batch=64)

@@ -659,7 +659,7 @@ def test_index_build_pair_equals_two_builds(hip_lib, B):
     Fw, H = 26, 32
     spec = ModelSpec("wdl", C=13, S=26, E=16, cate_index_size=8000, hidden=[64, H], Fw=Fw)
     eng = CTREngine(spec, max_batch=B, init="none", adam="lazy")
-    assert eng.index_pair
+    assert eng.wide_lazy
     b = make_batch(B, cate_index_size=8000, wide_fields=Fw, seed=B)
     b["cate_feats"][0, :4] = [0, 0, 5, 5]
     b["wide_feats"][1, :3] = [Fw, Fw + H - 1, Fw]

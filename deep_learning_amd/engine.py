@@ -85,6 +85,11 @@ class ModelSpec:
     cross_layers: layers of a Deep & Cross network (test_model/DCN.py:73-96) on the tower input of
     the dnn_pipeline / dnn_cate / dnn_multi / dnn_multi_cate models, its output joining the tower's
     in the one output layer (parameters cross_layer_%d, cross_bias_%d, cross_res); 0: none.
+    afm_attention: attention units A of an attentional pairwise-interaction branch (the
+    Pair-wise_Interaction_Layer and attention_net of test_model/AFM.py:63-129) over the S + M
+    embedded fields of the same four models, its logit added to the tower's (and the cross
+    network's); parameters attention_w [E, A], attention_b [1, A], attention_h [1, A],
+    attention_p [E, 1], no regulariser; 0: none.
     wide_optimizer: "adam" (the reference's one optimizer) or "ftrl" (wdl only): wdl_weights trained
     by TF1 FtrlOptimizer(wide_lr, learning_rate_power=-0.5, initial_accumulator_value=0.1,
     l1_regularization_strength=wide_l1, l2_regularization_strength=wide_l2), the loss's L2 term on
@@ -93,12 +98,13 @@ class ModelSpec:
 
     CROSS_MODELS = ("dnn_pipeline", "dnn_cate", "dnn_multi", "dnn_multi_cate")
     CROSS_MAX_LAYERS, CROSS_MAX_IN = 4, 1024     # csrc/cross.hip
+    AFM_MAX_ATT, AFM_MAX_FIELDS, AFM_EMB = 32, 64, (8, 16, 32)     # csrc/afm.hip
 
     def __init__(self, model, C=13, V=0, S=26, E=16, cate_index_size=1000, hidden=(400, 400, 400),
                  multi_ranges=(), Fw=0, lr=0.001, l2=1e-5, decay_steps=10000000, decay_rate=0.9,
                  beta1=0.9, beta2=0.999, eps=1e-8, logloss_eps=1e-7, tower="f32", dropout_keep_deep=None,
                  dropout_keep_fm=None, pos_weight=1.0, cross_layers=0, wide_optimizer="adam", wide_lr=None,
-                 wide_l1=0.0, wide_l2=0.0):
+                 wide_l1=0.0, wide_l2=0.0, afm_attention=0):
         if model not in FAMILIES:
             raise ValueError("unsupported model %r" % model)
         if wide_optimizer not in ("adam", "ftrl"):
@@ -116,6 +122,9 @@ class ModelSpec:
         if int(cross_layers) != cross_layers or cross_layers < 0:
             raise ValueError("cross_layers must be an integer >= 0, got %r" % (cross_layers,))
         self.cross_layers = int(cross_layers)
+        if int(afm_attention) != afm_attention or afm_attention < 0:
+            raise ValueError("afm_attention must be an integer >= 0, got %r" % (afm_attention,))
+        self.afm_attention = int(afm_attention)
         pos_weight = float(pos_weight)
         if not (math.isfinite(pos_weight) and pos_weight > 0.0):
             raise ValueError("pos_weight must be finite and > 0, got %r" % (pos_weight,))
@@ -169,6 +178,27 @@ class ModelSpec:
             if self.cross_layers > self.CROSS_MAX_LAYERS or self.deep_in > self.CROSS_MAX_IN:
                 raise ValueError("cross_layers: at most %d layers on at most %d tower-input columns, got %d on %d"
                                  % (self.CROSS_MAX_LAYERS, self.CROSS_MAX_IN, self.cross_layers, self.deep_in))
+        if self.afm_attention:
+            if model not in self.CROSS_MODELS:
+                raise ValueError("afm_attention: the attentional interactions join the tower of %s only, not %s"
+                                 % (", ".join(self.CROSS_MODELS), model))
+            if tower == "bf16":
+                raise ValueError("afm_attention: not supported with tower='bf16' (the branch reads the f32 "
+                                 "tower input)")
+            if self.dropout and self.dropout[0] < 1.0:
+                raise ValueError("afm_attention: not supported with tower-input dropout (dropout_keep_deep[0] < 1 "
+                                 "rewrites x0 in place; the branch reads the undropped fields)")
+            if (self.afm_attention > self.AFM_MAX_ATT or not 2 <= self.afm_fields <= self.AFM_MAX_FIELDS
+                    or self.E not in self.AFM_EMB):
+                raise ValueError("afm_attention: at most %d attention units on 2 to %d embedded fields of size %s, "
+                                 "got %d on %d fields of size %d"
+                                 % (self.AFM_MAX_ATT, self.AFM_MAX_FIELDS, " / ".join(map(str, self.AFM_EMB)),
+                                    self.afm_attention, self.afm_fields, self.E))
+
+    @property
+    def afm_fields(self):
+        """The fields the attentional interactions pair: single-valued, then pooled slots."""
+        return self.S + self.M
 
     @property
     def ftrl_lr(self):
@@ -551,6 +581,20 @@ class CTREngine:
             self.cross_s, self.z_cross = z(B, self.cross), z(B)
             self.cross_blocks = call_int("dl_cross_grid", B)
             self.cross_slab = z(self.cross_blocks, self.cross_n)
+        # attentional interactions (ModelSpec.afm_attention, csrc/afm.hip): the parameters as one vector
+        # [p (E) | h (A) | b (A) | W (E A)] with its Adam moments, the forward's softmax statistics
+        # [B, 2] and logit z_afm [B] (z_cross already added when both branches are on: the head's one
+        # z_extra), and the backward's per-block partial sums
+        self.afm = sp.afm_attention
+        if self.afm:
+            if type(self) is not CTREngine:
+                raise ValueError("afm_attention: not supported by %s" % type(self).__name__)
+            self.afm_n = E + 2 * self.afm + E * self.afm
+            self.aw = z(_ru(self.afm_n, 4))
+            self.am, self.av = torch.zeros_like(self.aw), torch.zeros_like(self.aw)
+            self.afm_stats, self.z_afm = z(B, 2), z(B)
+            self.afm_blocks = call_int("dl_afm_grid", B)
+            self.afm_slab = z(self.afm_blocks, self.afm_n)
         self.head_grid ="dl_wdl_head_grid" if self.wdl else "dl_head_grid"   # slab rows per batch size
         self.head_blocks = call_int(self.head_grid, B)
         self.head_slab = z(self.head_blocks, sp.fm_cols + H + 2)
@@ -713,6 +757,12 @@ class CTREngine:
             v = rng.standard_normal((2 * Lc + 1, D)) * math.sqrt(2.0 / (D + D))
             v[0] = rng.standard_normal(D) * math.sqrt(2.0 / (D + H + 1))
             self.cw[: self.cross_n].copy_(torch.from_numpy(v.astype(np.float32).reshape(-1)))
+        if self.afm:
+            # AFM.py:75-85: attention_w, attention_b ~ N(0, sqrt(2 / (A + E))); attention_h, attention_p ~ N(0, 1)
+            A, g = self.afm, math.sqrt(2.0 / (self.afm + sp.E))
+            P = {"attention_w": rng.standard_normal((sp.E, A)) * g, "attention_b": rng.standard_normal((1, A)) * g,
+                 "attention_h": rng.standard_normal((1, A)), "attention_p": rng.standard_normal((sp.E, 1))}
+            self.aw[: self.afm_n].copy_(torch.from_numpy(self._afm_pack(P)))
         if self.wide_lazy:
             self._wide_pack()
         torch.cuda.synchronize()
@@ -782,7 +832,34 @@ class CTREngine:
         self.w_head[: self.head_n].copy_(torch.from_numpy(w))
         if self.cross:
             self.cw[: self.cross_n].copy_(torch.from_numpy(self._cross_pack(P)))
+        if self.afm:
+            self.aw[: self.afm_n].copy_(torch.from_numpy(self._afm_pack(P)))
         torch.cuda.synchronize()
+
+    AFM_KEYS = ("attention_p", "attention_h", "attention_b", "attention_w")   # the device vector's order
+
+    def _afm_shapes(self):
+        E, A = self.spec.E, self.afm
+        return {"attention_p": (E, 1), "attention_h": (1, A), "attention_b": (1, A), "attention_w": (E, A)}
+
+    def _afm_pack(self, P):
+        """Reference-layout attention parameters (AFM.py:75-85) -> the device vector [p | h | b | W]."""
+        parts = []
+        for k, shp in self._afm_shapes().items():
+            a = np.asarray(P[k], np.float32)
+            if a.size != shp[0] * shp[1]:
+                raise ValueError("%s holds %d values, not %d x %d" % (k, a.size, shp[0], shp[1]))
+            parts.append(a.reshape(-1))
+        return np.concatenate(parts)
+
+    def _afm_unpack(self, vec):
+        """Inverse of _afm_pack on a device vector: {key: numpy in the reference's shape}."""
+        v = vec[: self.afm_n].cpu().numpy()
+        out, o = {}, 0
+        for k, shp in self._afm_shapes().items():
+            out[k] = v[o:o + shp[0] * shp[1]].reshape(shp).copy()
+            o += shp[0] * shp[1]
+        return out
 
     def _cross_keys(self):
         """Reference keys of the cross vector's (2L + 1) parts, in its order [c | w_l | b_l]."""
@@ -842,7 +919,8 @@ class CTREngine:
         """The dense parameters (hidden layers, head or wdl weights + bias) in the reference
         layout (numpy); the wide records are caught up first."""
         ww, wz, wn = self._wide_state()
-        P = self._export_dense(self.W, self.w_head, ww, getattr(self, "wb", None), getattr(self, "cw", None))
+        P = self._export_dense(self.W, self.w_head, ww, getattr(self, "wb", None), getattr(self, "cw", None),
+                               getattr(self, "aw", None))
         if self.ftrl:
             P.update(self._ftrl_export(wz, wn))
         return P
@@ -857,8 +935,10 @@ class CTREngine:
                  "v": self._export_dense(self.Wv, self.hv, None, self.wbv, None)}
             d.update(self._ftrl_export(wm, wv))
             return d
-        return {"m": self._export_dense(self.Wm, self.hm, wm, getattr(self, "wbm", None), getattr(self, "cm", None)),
-                "v": self._export_dense(self.Wv, self.hv, wv, getattr(self, "wbv", None), getattr(self, "cv", None))}
+        return {"m": self._export_dense(self.Wm, self.hm, wm, getattr(self, "wbm", None), getattr(self, "cm", None),
+                                        getattr(self, "am", None)),
+                "v": self._export_dense(self.Wv, self.hv, wv, getattr(self, "wbv", None), getattr(self, "cv", None),
+                                        getattr(self, "av", None))}
 
     # ------------------------------------------------------------------ wide records (wdl)
     FTRL_KEYS = ("ftrl/z", "ftrl/n")   # FTRL's linear and accumulator state of wdl_weights, [N + H, 1]
@@ -937,11 +1017,13 @@ class CTREngine:
              ptr(self.opt), ptr(self.wsq), ptr(self.wacc), _lib.stream_handle())
         self._wsq_step = self.steps
 
-    def _export_dense(self, Ws, head, ww, wb, cross=None):
+    def _export_dense(self, Ws, head, ww, wb, cross=None, afm=None):
         """Augmented hidden-layer matrices (bias row, x0 column order), the permuted head
-        vector, the wdl weights and the cross vector -> reference keys and layouts."""
+        vector, the wdl weights and the cross and attention vectors -> reference keys and layouts."""
         sp = self.spec
         P = self._cross_unpack(cross) if cross is not None else {}
+        if afm is not None:
+            P.update(self._afm_unpack(afm))
         dims = [self.D0] + sp.hidden
         for l in range(len(sp.hidden)):
             Wi = Ws[l].cpu().numpy()
@@ -1084,7 +1166,7 @@ class CTREngine:
         sp = self.spec
         if os.environ.get("DLAMD_FUSED_GATHER", "1") == "0" or not self.s3 or self.bf or sp.M:
             return False
-        if self.cross:   # the cross network reads x0's deep columns, which the fused forms leave unwritten
+        if self.cross or self.afm:   # both read x0's deep columns, which the fused forms leave unwritten
             return False
         pl = self.p_plane
         return (pl is not None and self.cat_col == 0 and sp.E in (8, 16, 32, 64) and 0 < sp.S <= 40
@@ -1390,15 +1472,20 @@ class CTREngine:
                     self.head_blocks, sp.F, self._keep_thr(k1), self._keep_inv(k1), self._keep_thr(k2),
                     self._keep_inv(k2), self.seed & 0xFFFFFFFFFFFFFFFF, ptr(self.opt), ptr(self.fm_keep), s)
             return
-        if self.cross:
+        if self.cross or self.afm:
             # x0 is complete here (in lazy training the first layer's fused row gather wrote its
-            # deep columns): s and z_cross, then the head with z_cross added to the logit
-            self._c("cross_fwd", "dl_cross_fwd", B, self.D0, self.cross, ptr(self.x0), self.in_ld[0], ptr(self.cw),
-                    ptr(self.cross_s), ptr(self.z_cross), s)
+            # deep columns): s and z_cross, z_afm (+ z_cross), then the head with that extra logit
+            if self.cross:
+                self._c("cross_fwd", "dl_cross_fwd", B, self.D0, self.cross, ptr(self.x0), self.in_ld[0],
+                        ptr(self.cw), ptr(self.cross_s), ptr(self.z_cross), s)
+            if self.afm:
+                self._c("afm_fwd", "dl_afm_fwd", B, sp.afm_fields, sp.E, self.afm, ptr(self.x0), self.in_ld[0],
+                        self.cat_col, ptr(self.aw), ptr(self.z_cross) if self.cross else None, ptr(self.afm_stats),
+                        ptr(self.z_afm), s)
             self._c("head", "dl_head_fwd_bwd_cross" + sw, B, sp.fm_cols, H, ptr(self.fm_out), self.fm_ld,
                     ptr(self.h[-1]), self.h_ld[-1], ptr(self.w_head), ptr(self.in_label), sp.logloss_eps, *scale,
-                    ptr(self.z_cross), ptr(self.score), ptr(self.z), ptr(self.dz), ptr(self.dh[-1]),
-                    ptr(self.head_slab), self.head_blocks, s)
+                    ptr(self.z_afm if self.afm else self.z_cross), ptr(self.score), ptr(self.z), ptr(self.dz),
+                    ptr(self.dh[-1]), ptr(self.head_slab), self.head_blocks, s)
             return
         self._c("head", "dl_head_fwd_bwd" + sw, B, sp.fm_cols, H, ptr(self.fm_out), self.fm_ld, ptr(self.h[-1]),
              self.h_ld[-1], ptr(self.w_head), ptr(self.in_label), sp.logloss_eps, *scale,
@@ -1489,6 +1576,11 @@ class CTREngine:
             self._c("cross_bwd", "dl_cross_bwd", B, self.D0, self.cross, ptr(self.x0), self.in_ld[0], ptr(self.cw),
                     ptr(self.cross_s), ptr(self.dz), ptr(self.dx0), self.dx_ld, self.cat_col, self.dx_cols,
                     ptr(self.cross_slab), self.cross_blocks, s)
+        if self.afm:
+            # the attentional interactions' share of dx0's field columns, likewise before the embedding backward
+            self._c("afm_bwd", "dl_afm_bwd", B, sp.afm_fields, sp.E, self.afm, ptr(self.x0), self.in_ld[0],
+                    self.cat_col, ptr(self.aw), ptr(self.afm_stats), ptr(self.dz), ptr(self.dx0), self.dx_ld, 0,
+                    ptr(self.afm_slab), self.afm_blocks, s)
         self._train_back(B, s, L)
         # the step's loss into the running sum (read once per epoch: loss_sum_end)
         width = self.head_slab.shape[1]
@@ -1677,6 +1769,10 @@ class CTREngine:
             self._c("adam_cross", "dl_adam_dense", ptr(self.cw), ptr(self.cm), ptr(self.cv), ptr(self.cross_slab),
                     call_int("dl_cross_grid", B), self.cross_n, self.cross_n, sp.l2, self.D0, ptr(self.opt), None,
                     ptr(self.opt[8:]), s)
+        if self.afm:
+            # attention Adam: no regulariser on these variables (AFM.py:137 has none on them)
+            self._c("adam_afm", "dl_adam_dense", ptr(self.aw), ptr(self.am), ptr(self.av), ptr(self.afm_slab),
+                    call_int("dl_afm_grid", B), self.afm_n, self.afm_n, 0.0, 0, ptr(self.opt), None, None, s)
         if self.lazy:
             return
         if sp.fm:

@@ -16,6 +16,9 @@ at 1); with weight_key, evaluation's logloss and calibration are weighted too.
 cross_layers=N (dnn_pipeline, dnn_cate, dnn_multi, dnn_multi_cate) adds an N-layer Deep & Cross
 network on the tower input, its output joining the tower's in the output layer.
 
+afm_attention=A (the same four models) adds the attentional pairwise interactions of the reference's
+test_model/AFM.py over the embedded fields, A attention units, its logit added to the tower's.
+
 wide_optimizer=ftrl wide_lr=0.05 wide_l1=1e-3 wide_l2=0 (wdl: models/wdl.py reads them from its args)
 train the wide weights with FTRL-proximal instead of Adam; L1 leaves most wide rows at exactly zero.
 
@@ -81,6 +84,8 @@ class ModelParams:
                 self.weight_key = v
             elif k == "cross_layers":   # a cross network beside the dnn_* tower, stored only when given
                 self.cross_layers = check_cross_layers(v, self.alg_name)
+            elif k == "afm_attention":   # attentional pairwise interactions beside the tower, likewise
+                self.afm_attention = check_afm_attention(v, self.alg_name)
             elif k in ("wide_optimizer", "wide_lr", "wide_l1", "wide_l2"):   # stored only when given, too
                 setattr(self, k, check_wide_option(k, v, self.alg_name))
             else:
@@ -116,6 +121,22 @@ def check_cross_layers(v, alg_name):
         raise SystemExit("cross_layers=%s must lie in [0, %d]" % (v, ModelSpec.CROSS_MAX_LAYERS))
     if n and alg_name not in ModelSpec.CROSS_MODELS:
         raise SystemExit("cross_layers=%s: the cross network joins the tower of %s only, not %s"
+                         % (v, ", ".join(ModelSpec.CROSS_MODELS), alg_name))
+    return n
+
+
+def check_afm_attention(v, alg_name):
+    """afm_attention=A as an int; refuses (SystemExit) anything but an integer in [0, AFM_MAX_ATT],
+    and A > 0 for a model other than the dnn_* ones."""
+    from .engine import ModelSpec
+    try:
+        n = int(v)
+    except ValueError:
+        raise SystemExit("afm_attention=%s is not an integer" % v)
+    if n < 0 or n > ModelSpec.AFM_MAX_ATT:
+        raise SystemExit("afm_attention=%s must lie in [0, %d]" % (v, ModelSpec.AFM_MAX_ATT))
+    if n and alg_name not in ModelSpec.CROSS_MODELS:
+        raise SystemExit("afm_attention=%s: the attentional interactions join the tower of %s only, not %s"
                          % (v, ", ".join(ModelSpec.CROSS_MODELS), alg_name))
     return n
 

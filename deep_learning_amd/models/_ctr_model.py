@@ -54,6 +54,8 @@ def _spec_from_args(model, args):
         kw.update(pos_weight=float(args.pos_weight))
     if getattr(args, "cross_layers", None) is not None:   # local_run's cross_layers= (stored only when given)
         kw.update(cross_layers=int(args.cross_layers))
+    if getattr(args, "afm_attention", None) is not None:   # local_run's afm_attention= (stored only when given)
+        kw.update(afm_attention=int(args.afm_attention))
     return ModelSpec(model, **kw)
 
 
@@ -231,6 +233,8 @@ def _adam_state(eng):
     out["adam/hm"], out["adam/hv"] = eng.hm.cpu().numpy(), eng.hv.cpu().numpy()
     if eng.cross:   # the cross vector's moments, in the device layout (engine.py _cross_pack)
         out["adam/cm"], out["adam/cv"] = eng.cm.cpu().numpy(), eng.cv.cpu().numpy()
+    if eng.afm:     # the attention vector's moments, in the device layout (engine.py _afm_pack)
+        out["adam/am"], out["adam/av"] = eng.am.cpu().numpy(), eng.av.cpu().numpy()
     for l in range(len(eng.W)):
         out["adam/Wm%d" % l] = eng.Wm[l].cpu().numpy()
         out["adam/Wv%d" % l] = eng.Wv[l].cpu().numpy()
@@ -251,6 +255,9 @@ def _load_adam_state(eng, d):
     if eng.cross:
         eng.cm.copy_(torch.from_numpy(d["adam/cm"]))
         eng.cv.copy_(torch.from_numpy(d["adam/cv"]))
+    if eng.afm:
+        eng.am.copy_(torch.from_numpy(d["adam/am"]))
+        eng.av.copy_(torch.from_numpy(d["adam/av"]))
     for l in range(len(eng.W)):
         eng.Wm[l].copy_(torch.from_numpy(d["adam/Wm%d" % l]))
         eng.Wv[l].copy_(torch.from_numpy(d["adam/Wv%d" % l]))

@@ -182,6 +182,9 @@ class ShardedCTREngine(CTREngine):
         if spec.cross_layers:
             raise ValueError("cross_layers: not supported by ShardedCTREngine (the cross parameters' gradients "
                              "are not part of the flat all-reduce)")
+        if spec.afm_attention:
+            raise ValueError("afm_attention: not supported by ShardedCTREngine (the attention parameters' "
+                             "gradients are not part of the flat all-reduce)")
         # the status ring holds 4 reports (slot k & 3) and the host reads report k only after
         # k + lag was submitted: lag <= 3, or report k + 4 overwrites k before it is read
         if not 0 <= int(lag) <= 3:

@@ -491,6 +491,34 @@ int dl_head_fwd_bwd_cross_weighted(int32_t B, int32_t fm_cols, int32_t H, const 
                                    float* score, float* z_out, float* dz, float* dh, float* slab,
                                    int32_t slab_blocks, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Attentional pairwise interactions (AFM) beside the dnn_* tower: the pairwise-interaction and
+ * attention layers of test_model/AFM.py:63-129 (variables :75-85, pair loop :92-101, attention
+ * :104-118, projection :121-129) on the F embedded fields of x0 [B, ld], field i in columns
+ * [x_col0 + i E, x_col0 + (i + 1) E).  Over the P = F (F - 1) / 2 pairs i < j:
+ *   q_ij = e_i * e_j;  u_ij = q_ij W + b;  s_ij = h . relu(u_ij);
+ *   a_ij = exp(s_ij - max s) / sum exp(s - max s);  z_afm = (sum a_ij q_ij) . p
+ * params: [p (E) | h (A) | b (A) | W (E A, row-major [E][A])].  2 <= F <= 64, E one of 8, 16, 32,
+ * 1 <= A <= 32; anything else is refused.
+ * dl_afm_fwd writes z_out[b] = z_afm[b] + (z_add ? z_add[b] : 0) (z_add: the cross network's
+ * z_cross, so the head's one z_extra carries both) and stats [B, 2] = {max s, sum exp(s - max)};
+ * nothing per pair goes to HBM.  dl_afm_bwd recomputes q, u and s from x0 and, with
+ *   ds_ij = a_ij dz (q_ij . p - z_afm);  g_ij = ds_ij (h * [u_ij > 0]);  dq_ij = a_ij dz p + W g_ij
+ * adds de_i += dq_ij * e_j, de_j += dq_ij * e_i INTO dx0 [B, dx_ld] columns [dx_col0, dx_col0 + F E)
+ * and leaves the batch sums of (dp, dh, db, dW) as per-block partials slab[block][E + 2 A + E A]
+ * in the layout of params (dl_afm_grid(B) blocks, at most 512; dl_adam_dense sums them in slab
+ * order).  No atomics: the same inputs give the same bits on every run. */
+int dl_afm_grid(int32_t B);
+int dl_afm_fwd(int32_t B, int32_t F, int32_t E, int32_t A, const float* x0, int32_t ld, int32_t x_col0,
+               const float* params, const float* z_add, float* stats, float* z_out, void* stream);
+int dl_afm_bwd(int32_t B, int32_t F, int32_t E, int32_t A, const float* x0, int32_t ld, int32_t x_col0,
+               const float* params, const float* stats, const float* dz, float* dx0, int32_t dx_ld,
+               int32_t dx_col0, float* slab, int32_t slab_rows, void* stream);
+/* The f32 vector-rate yardstick of scripts/afm_bench.py: `blocks` blocks of 256 threads, each thread
+ * 16 independent chains of `iters` FMAs (32 * iters FLOP a thread, no memory traffic); out needs
+ * blocks * 256 floats (n_out is checked). */
+int dl_vfma_probe(float* out, int64_t n_out, int32_t blocks, int32_t iters, void* stream);
+
 /* Wide&Deep cross logit, forward and backward fused (models/wdl.py:225-275):
  * z = sum_f w[wide_f] + sum_j w[Fw+j] h_j + bias[0] (w = wdl_weights [w_rows]; the
  * deep-output rows Fw..Fw+H alias wide ids); sigmoid + eps-log-loss as dl_head_fwd_bwd.

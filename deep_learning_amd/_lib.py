@@ -154,7 +154,10 @@ SIGNATURES = {
     "dl_afm_grid": (I32, [I32]),
     "dl_afm_fwd": (I32, [I32, I32, I32, I32, P, I32, I32, P, P, P, P, P]),
     "dl_afm_bwd": (I32, [I32, I32, I32, I32, P, I32, I32, P, P, P, P, I32, I32, P, I32, P]),
-    "dl_loss_accumulate_weighted": (I32, [P, I32, I32, I32, P, P, F, P, P, P]),
+    "dl_pnn_grid": (I32, [I32]),
+    "dl_pnn_inner_fwd": (I32, [I32, I32, I32, I32, P, I32, I32, P, P, I32, P, I32, P]),
+    "dl_pnn_inner_bwd": (I32, [I32, I32, I32, I32, P, I32, I32, P, P, I32, P, I32, I32, P, I32, P]),
+    "dl_loss_accumulate_weighted":(I32, [P, I32, I32, I32, P, P, F, P, P, P]),
     "dl_slab_fold_rows": (I32, [P, I32, I32, I32, I32, P, I64, P, P]),
     "dl_adam_begin_step": (I32, [P, F, F, P]),
     "dl_step_guard": (I32, [P, P, P]),

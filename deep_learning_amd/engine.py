@@ -90,6 +90,11 @@ class ModelSpec:
     embedded fields of the same four models, its logit added to the tower's (and the cross
     network's); parameters attention_w [E, A], attention_b [1, A], attention_h [1, A],
     attention_p [E, 1], no regulariser; 0: none.
+    pnn: "inner" puts the inner-product layer of test_model/PNN.py:78-83 in front of the same four
+    models' tower: lp_i = || sum_f theta[i, f] e_f || over the S + M embedded fields, added to layer
+    0's pre-activation before its ReLU (hidden[0] = D1); parameter product-quadratic-inner [D1, F],
+    no regulariser; the reference's product-linear and product-bias are layer 0 itself; None: off
+    (DESIGN 4m).
     wide_optimizer: "adam" (the reference's one optimizer) or "ftrl" (wdl only): wdl_weights trained
     by TF1 FtrlOptimizer(wide_lr, learning_rate_power=-0.5, initial_accumulator_value=0.1,
     l1_regularization_strength=wide_l1, l2_regularization_strength=wide_l2), the loss's L2 term on
@@ -99,12 +104,13 @@ class ModelSpec:
     CROSS_MODELS = ("dnn_pipeline", "dnn_cate", "dnn_multi", "dnn_multi_cate")
     CROSS_MAX_LAYERS, CROSS_MAX_IN = 4, 1024     # csrc/cross.hip
     AFM_MAX_ATT, AFM_MAX_FIELDS, AFM_EMB = 32, 64, (8, 16, 32)     # csrc/afm.hip
+    PNN_MAX_FIELDS, PNN_EMB = 64, (8, 16, 32)                      # csrc/pnn.hip
 
     def __init__(self, model, C=13, V=0, S=26, E=16, cate_index_size=1000, hidden=(400, 400, 400),
                  multi_ranges=(), Fw=0, lr=0.001, l2=1e-5, decay_steps=10000000, decay_rate=0.9,
                  beta1=0.9, beta2=0.999, eps=1e-8, logloss_eps=1e-7, tower="f32", dropout_keep_deep=None,
                  dropout_keep_fm=None, pos_weight=1.0, cross_layers=0, wide_optimizer="adam", wide_lr=None,
-                 wide_l1=0.0, wide_l2=0.0, afm_attention=0):
+                 wide_l1=0.0, wide_l2=0.0, afm_attention=0, pnn=None):
         if model not in FAMILIES:
             raise ValueError("unsupported model %r" % model)
         if wide_optimizer not in ("adam", "ftrl"):
@@ -125,6 +131,12 @@ class ModelSpec:
         if int(afm_attention) != afm_attention or afm_attention < 0:
             raise ValueError("afm_attention must be an integer >= 0, got %r" % (afm_attention,))
         self.afm_attention = int(afm_attention)
+        if pnn == "outer":
+            raise ValueError("pnn='outer': the outer-product layer (PNN.py:85-91, an E * E first-layer input) is "
+                             "not built; pnn='inner' is")
+        if pnn not in (None, "inner"):
+            raise ValueError("pnn must be None or 'inner', got %r" % (pnn,))
+        self.pnn = pnn
         pos_weight = float(pos_weight)
         if not (math.isfinite(pos_weight) and pos_weight > 0.0):
             raise ValueError("pos_weight must be finite and > 0, got %r" % (pos_weight,))
@@ -194,10 +206,29 @@ class ModelSpec:
                                  "got %d on %d fields of size %d"
                                  % (self.AFM_MAX_ATT, self.AFM_MAX_FIELDS, " / ".join(map(str, self.AFM_EMB)),
                                     self.afm_attention, self.afm_fields, self.E))
+        if self.pnn:
+            if model not in self.CROSS_MODELS:
+                raise ValueError("pnn: the product layer feeds the tower of %s only, not %s"
+                                 % (", ".join(self.CROSS_MODELS), model))
+            if tower == "bf16":
+                raise ValueError("pnn: not supported with tower='bf16' (the product layer reads the f32 tower "
+                                 "input and finishes the f32 first layer)")
+            if self.dropout and self.dropout[0] < 1.0:
+                raise ValueError("pnn: not supported with tower-input dropout (dropout_keep_deep[0] < 1 rewrites "
+                                 "x0 in place; the product layer reads the undropped fields)")
+            if self.dropout and self.dropout[1] < 1.0:
+                raise ValueError("pnn: not supported with dropout on the first layer's output "
+                                 "(dropout_keep_deep[1] < 1: that layer's ReLU and dropout live in the GEMM "
+                                 "epilogue the product layer replaces)")
+            if not 2 <= self.afm_fields <= self.PNN_MAX_FIELDS or self.E not in self.PNN_EMB:
+                raise ValueError("pnn: 2 to %d embedded fields of size %s, got %d fields of size %d"
+                                 % (self.PNN_MAX_FIELDS, " / ".join(map(str, self.PNN_EMB)), self.afm_fields,
+                                    self.E))
 
     @property
     def afm_fields(self):
-        """The fields the attentional interactions pair: single-valued, then pooled slots."""
+        """The fields the attentional interactions pair (and the product layer mixes): single-valued,
+        then pooled slots."""
         return self.S + self.M
 
     @property
@@ -595,6 +626,17 @@ class CTREngine:
             self.afm_stats, self.z_afm = z(B, 2), z(B)
             self.afm_blocks = call_int("dl_afm_grid", B)
             self.afm_slab = z(self.afm_blocks, self.afm_n)
+        # product layer (ModelSpec.pnn, csrc/pnn.hip): theta [D1, F] with its Adam moments and the
+        # backward's per-block partial sums; lp itself is added into h[0] and kept nowhere
+        self.pnn = sp.pnn
+        if self.pnn:
+            if type(self) is not CTREngine:
+                raise ValueError("pnn: not supported by %s" % type(self).__name__)
+            self.pnn_n = sp.hidden[0] * sp.afm_fields
+            self.pw = z(_ru(self.pnn_n, 4))
+            self.pm, self.pv = torch.zeros_like(self.pw), torch.zeros_like(self.pw)
+            self.pnn_blocks = call_int("dl_pnn_grid", B)
+            self.pnn_slab = z(self.pnn_blocks, self.pnn_n)
         self.head_grid ="dl_wdl_head_grid" if self.wdl else "dl_head_grid"   # slab rows per batch size
         self.head_blocks = call_int(self.head_grid, B)
         self.head_slab = z(self.head_blocks, sp.fm_cols + H + 2)
@@ -763,6 +805,10 @@ class CTREngine:
             P = {"attention_w": rng.standard_normal((sp.E, A)) * g, "attention_b": rng.standard_normal((1, A)) * g,
                  "attention_h": rng.standard_normal((1, A)), "attention_p": rng.standard_normal((sp.E, 1))}
             self.aw[: self.afm_n].copy_(torch.from_numpy(self._afm_pack(P)))
+        if self.pnn:
+            # PNN.py:57: product-quadratic-inner ~ N(0, 0.01)
+            v = rng.standard_normal((sp.hidden[0], sp.afm_fields)) * 0.01
+            self.pw[: self.pnn_n].copy_(torch.from_numpy(self._pnn_pack({self.PNN_KEY: v})))
         if self.wide_lazy:
             self._wide_pack()
         torch.cuda.synchronize()
@@ -834,7 +880,24 @@ class CTREngine:
             self.cw[: self.cross_n].copy_(torch.from_numpy(self._cross_pack(P)))
         if self.afm:
             self.aw[: self.afm_n].copy_(torch.from_numpy(self._afm_pack(P)))
+        if self.pnn:
+            self.pw[: self.pnn_n].copy_(torch.from_numpy(self._pnn_pack(P)))
         torch.cuda.synchronize()
+
+    PNN_KEY = "product-quadratic-inner"   # PNN.py:57, [D1, F]: the device vector is its row-major image
+
+    def _pnn_pack(self, P):
+        """Reference-layout theta [D1, F] -> the device vector."""
+        D1, F = self.spec.hidden[0], self.spec.afm_fields
+        a = np.asarray(P[self.PNN_KEY], np.float32)
+        if a.shape != (D1, F):
+            raise ValueError("%s has shape %r, not (%d, %d)" % (self.PNN_KEY, a.shape, D1, F))
+        return np.ascontiguousarray(a).reshape(-1)
+
+    def _pnn_unpack(self, vec):
+        """Inverse of _pnn_pack on a device vector."""
+        D1, F = self.spec.hidden[0], self.spec.afm_fields
+        return {self.PNN_KEY: vec[: self.pnn_n].cpu().numpy().reshape(D1, F).copy()}
 
     AFM_KEYS = ("attention_p", "attention_h", "attention_b", "attention_w")   # the device vector's order
 
@@ -920,7 +983,7 @@ class CTREngine:
         layout (numpy); the wide records are caught up first."""
         ww, wz, wn = self._wide_state()
         P = self._export_dense(self.W, self.w_head, ww, getattr(self, "wb", None), getattr(self, "cw", None),
-                               getattr(self, "aw", None))
+                               getattr(self, "aw", None), getattr(self, "pw", None))
         if self.ftrl:
             P.update(self._ftrl_export(wz, wn))
         return P
@@ -936,9 +999,9 @@ class CTREngine:
             d.update(self._ftrl_export(wm, wv))
             return d
         return {"m": self._export_dense(self.Wm, self.hm, wm, getattr(self, "wbm", None), getattr(self, "cm", None),
-                                        getattr(self, "am", None)),
+                                        getattr(self, "am", None), getattr(self, "pm", None)),
                 "v": self._export_dense(self.Wv, self.hv, wv, getattr(self, "wbv", None), getattr(self, "cv", None),
-                                        getattr(self, "av", None))}
+                                        getattr(self, "av", None), getattr(self, "pv", None))}
 
     # ------------------------------------------------------------------ wide records (wdl)
     FTRL_KEYS = ("ftrl/z", "ftrl/n")   # FTRL's linear and accumulator state of wdl_weights, [N + H, 1]
@@ -1017,13 +1080,16 @@ class CTREngine:
              ptr(self.opt), ptr(self.wsq), ptr(self.wacc), _lib.stream_handle())
         self._wsq_step = self.steps
 
-    def _export_dense(self, Ws, head, ww, wb, cross=None, afm=None):
+    def _export_dense(self, Ws, head, ww, wb, cross=None, afm=None, pnn=None):
         """Augmented hidden-layer matrices (bias row, x0 column order), the permuted head
-        vector, the wdl weights and the cross and attention vectors -> reference keys and layouts."""
+        vector, the wdl weights and the cross, attention and product vectors -> reference keys and
+        layouts."""
         sp = self.spec
         P = self._cross_unpack(cross) if cross is not None else {}
         if afm is not None:
             P.update(self._afm_unpack(afm))
+        if pnn is not None:
+            P.update(self._pnn_unpack(pnn))
         dims = [self.D0] + sp.hidden
         for l in range(len(sp.hidden)):
             Wi = Ws[l].cpu().numpy()
@@ -1166,7 +1232,7 @@ class CTREngine:
         sp = self.spec
         if os.environ.get("DLAMD_FUSED_GATHER", "1") == "0" or not self.s3 or self.bf or sp.M:
             return False
-        if self.cross or self.afm:   # both read x0's deep columns, which the fused forms leave unwritten
+        if self.cross or self.afm or self.pnn:   # all read x0's deep columns, which the fused forms leave unwritten
             return False
         pl = self.p_plane
         return (pl is not None and self.cat_col == 0 and sp.E in (8, 16, 32, 64) and 0 < sp.S <= 40
@@ -1388,6 +1454,11 @@ class CTREngine:
             x = self.x0
             for l, hdim in enumerate(sp.hidden):
                 bits = (ptr(self.hbits[l]), self.hbits_ld[l]) if l < len(self.hbits) else (None, 0)
+                # product layer: layer 0 stores its pre-activation; dl_pnn_inner_fwd adds lp and applies
+                # the ReLU (and writes the sign bitmask) in place
+                epi = 0 if l == 0 and self.pnn else 1
+                if l == 0 and self.pnn:
+                    pnn_bits, bits = bits, (None, 0)
                 if l == 0 and fused == "rows":
                     # the training form: rows_u through the inverse map (deep slots after the FM
                     # slots), x0's deep columns written for the weight gradient
@@ -1395,7 +1466,7 @@ class CTREngine:
                     self._c("gemm_fwd_l0", "dl_gemm_s3_nt_gather_rows", B, hdim, self.in_ld[0], ptr(x), self.in_ld[0],
                             ptr(self.rows_u), self.rows_u.shape[0], sp.E, ptr(self.idx_inv[off:]), self.n_slot,
                             self.n_rep, sp.S, sp.E, ptr(self.WTp[0]), self.in_ld[0], self.in_ld[0] * self.out_ld[0],
-                            ptr(self.h[0]), self.h_ld[0], 1, *bits, s)
+                            ptr(self.h[0]), self.h_ld[0], epi, *bits, s)
                 elif l == 0 and fused == "tab":
                     # predict's table form: the rows' offsets staged from gtab
                     FL = self._flat_layout(B)
@@ -1417,14 +1488,26 @@ class CTREngine:
                 else:
                     self._c("gemm_fwd_l%d" % l, "dl_gemm_s3_nt_bits", B, hdim, self.in_ld[l], ptr(x), self.in_ld[l],
                             ptr(self.WTp[l]), self.in_ld[l], self.in_ld[l] * self.out_ld[l], ptr(self.h[l]),
-                            self.h_ld[l], 1, None, 0, *bits, s)
+                            self.h_ld[l], epi, None, 0, *bits, s)
+                if l == 0 and self.pnn:
+                    self._pnn_fwd(B, pnn_bits, s)
                 x = self.h[l]
         else:
             x = self.x0
             for l, hdim in enumerate(sp.hidden):
                 self._c("gemm_fwd_l%d" % l, "dl_gemm_f32", 0, 0, B, hdim, self.in_ld[l], ptr(x), self.in_ld[l],
-                        ptr(self.W[l]), self.out_ld[l], ptr(self.h[l]), self.h_ld[l], 1, None, 0, 1, 0, s)
+                        ptr(self.W[l]), self.out_ld[l], ptr(self.h[l]), self.h_ld[l],
+                        0 if l == 0 and self.pnn else 1, None, 0, 1, 0, s)
+                if l == 0 and self.pnn:   # (the f32 path reads the ReLU's sign from h[0] itself)
+                    self._pnn_fwd(B, (None, 0), s)
                 x = self.h[l]
+
+    def _pnn_fwd(self, B, bits, s):
+        """h[0] = relu(h[0] + lp): the product layer on layer 0's stored pre-activation (x0 is complete:
+        in lazy training the first layer's fused row gather wrote its deep columns)."""
+        sp = self.spec
+        self._c("pnn_fwd", "dl_pnn_inner_fwd", B, sp.afm_fields, sp.E, sp.hidden[0], ptr(self.x0), self.in_ld[0],
+                self.cat_col, ptr(self.pw), ptr(self.h[0]), self.h_ld[0], *bits, s)
 
     def _head(self, B, s, train):
         """The output layer, the loss and its gradients dz and dh[-1]: the wdl cross logit (wide
@@ -1581,6 +1664,11 @@ class CTREngine:
             self._c("afm_bwd", "dl_afm_bwd", B, sp.afm_fields, sp.E, self.afm, ptr(self.x0), self.in_ld[0],
                     self.cat_col, ptr(self.aw), ptr(self.afm_stats), ptr(self.dz), ptr(self.dx0), self.dx_ld, 0,
                     ptr(self.afm_slab), self.afm_blocks, s)
+        if self.pnn:
+            # the product layer's share, from the ReluGrad-masked dh[0] the tower's backward formed
+            self._c("pnn_bwd", "dl_pnn_inner_bwd", B, sp.afm_fields, sp.E, sp.hidden[0], ptr(self.x0), self.in_ld[0],
+                    self.cat_col, ptr(self.pw), ptr(self.dh[0]), self.h_ld[0], ptr(self.dx0), self.dx_ld, 0,
+                    ptr(self.pnn_slab), self.pnn_blocks, s)
         self._train_back(B, s, L)
         # the step's loss into the running sum (read once per epoch: loss_sum_end)
         width = self.head_slab.shape[1]
@@ -1773,6 +1861,10 @@ class CTREngine:
             # attention Adam: no regulariser on these variables (AFM.py:137 has none on them)
             self._c("adam_afm", "dl_adam_dense", ptr(self.aw), ptr(self.am), ptr(self.av), ptr(self.afm_slab),
                     call_int("dl_afm_grid", B), self.afm_n, self.afm_n, 0.0, 0, ptr(self.opt), None, None, s)
+        if self.pnn:
+            # theta's Adam: no regulariser (PNN.py:136-139 has none on it)
+            self._c("adam_pnn", "dl_adam_dense", ptr(self.pw), ptr(self.pm), ptr(self.pv), ptr(self.pnn_slab),
+                    call_int("dl_pnn_grid", B), self.pnn_n, self.pnn_n, 0.0, 0, ptr(self.opt), None, None, s)
         if self.lazy:
             return
         if sp.fm:

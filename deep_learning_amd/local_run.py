@@ -19,6 +19,9 @@ network on the tower input, its output joining the tower's in the output layer.
 afm_attention=A (the same four models) adds the attentional pairwise interactions of the reference's
 test_model/AFM.py over the embedded fields, A attention units, its logit added to the tower's.
 
+pnn=inner (the same four models) puts the inner-product layer of the reference's test_model/PNN.py in
+front of the tower: the norm of a learned mix of the embedded fields, per unit of the first hidden layer.
+
 wide_optimizer=ftrl wide_lr=0.05 wide_l1=1e-3 wide_l2=0 (wdl: models/wdl.py reads them from its args)
 train the wide weights with FTRL-proximal instead of Adam; L1 leaves most wide rows at exactly zero.
 
@@ -86,6 +89,8 @@ class ModelParams:
                 self.cross_layers = check_cross_layers(v, self.alg_name)
             elif k == "afm_attention":   # attentional pairwise interactions beside the tower, likewise
                 self.afm_attention = check_afm_attention(v, self.alg_name)
+            elif k == "pnn":             # the product layer in front of the tower, likewise
+                self.pnn = check_pnn(v, self.alg_name)
             elif k in ("wide_optimizer", "wide_lr", "wide_l1", "wide_l2"):   # stored only when given, too
                 setattr(self, k, check_wide_option(k, v, self.alg_name))
             else:
@@ -139,6 +144,19 @@ def check_afm_attention(v, alg_name):
         raise SystemExit("afm_attention=%s: the attentional interactions join the tower of %s only, not %s"
                          % (v, ", ".join(ModelSpec.CROSS_MODELS), alg_name))
     return n
+
+
+def check_pnn(v, alg_name):
+    """pnn=inner as a string; refuses (SystemExit) any other value, and a model other than the dnn_* ones."""
+    from .engine import ModelSpec
+    if v == "outer":
+        raise SystemExit("pnn=outer: the outer-product layer is not built; pnn=inner is")
+    if v != "inner":
+        raise SystemExit("pnn=%s must be inner" % v)
+    if alg_name not in ModelSpec.CROSS_MODELS:
+        raise SystemExit("pnn=%s: the product layer feeds the tower of %s only, not %s"
+                         % (v, ", ".join(ModelSpec.CROSS_MODELS), alg_name))
+    return v
 
 
 def check_wide_option(k, v, alg_name):

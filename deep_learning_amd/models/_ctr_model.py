@@ -56,6 +56,8 @@ def _spec_from_args(model, args):
         kw.update(cross_layers=int(args.cross_layers))
     if getattr(args, "afm_attention", None) is not None:   # local_run's afm_attention= (stored only when given)
         kw.update(afm_attention=int(args.afm_attention))
+    if getattr(args, "pnn", None) is not None:             # local_run's pnn= (stored only when given)
+        kw.update(pnn=args.pnn)
     return ModelSpec(model, **kw)
 
 
@@ -235,6 +237,8 @@ def _adam_state(eng):
         out["adam/cm"], out["adam/cv"] = eng.cm.cpu().numpy(), eng.cv.cpu().numpy()
     if eng.afm:     # the attention vector's moments, in the device layout (engine.py _afm_pack)
         out["adam/am"], out["adam/av"] = eng.am.cpu().numpy(), eng.av.cpu().numpy()
+    if eng.pnn:     # theta's moments, row-major [D1, F] as the device vector (engine.py _pnn_pack)
+        out["adam/pm"], out["adam/pv"] = eng.pm.cpu().numpy(), eng.pv.cpu().numpy()
     for l in range(len(eng.W)):
         out["adam/Wm%d" % l] = eng.Wm[l].cpu().numpy()
         out["adam/Wv%d" % l] = eng.Wv[l].cpu().numpy()
@@ -258,6 +262,9 @@ def _load_adam_state(eng, d):
     if eng.afm:
         eng.am.copy_(torch.from_numpy(d["adam/am"]))
         eng.av.copy_(torch.from_numpy(d["adam/av"]))
+    if eng.pnn:
+        eng.pm.copy_(torch.from_numpy(d["adam/pm"]))
+        eng.pv.copy_(torch.from_numpy(d["adam/pv"]))
     for l in range(len(eng.W)):
         eng.Wm[l].copy_(torch.from_numpy(d["adam/Wm%d" % l]))
         eng.Wv[l].copy_(torch.from_numpy(d["adam/Wv%d" % l]))

@@ -185,6 +185,9 @@ class ShardedCTREngine(CTREngine):
         if spec.afm_attention:
             raise ValueError("afm_attention: not supported by ShardedCTREngine (the attention parameters' "
                              "gradients are not part of the flat all-reduce)")
+        if spec.pnn:
+            raise ValueError("pnn: not supported by ShardedCTREngine (theta's gradient is not part of the flat "
+                             "all-reduce)")
         # the status ring holds 4 reports (slot k & 3) and the host reads report k only after
         # k + lag was submitted: lag <= 3, or report k + 4 overwrites k before it is read
         if not 0 <= int(lag) <= 3:

@@ -514,6 +514,31 @@ int dl_afm_fwd(int32_t B, int32_t F, int32_t E, int32_t A, const float* x0, int3
 int dl_afm_bwd(int32_t B, int32_t F, int32_t E, int32_t A, const float* x0, int32_t ld, int32_t x_col0,
                const float* params, const float* stats, const float* dz, float* dx0, int32_t dx_ld,
                int32_t dx_col0, float* slab, int32_t slab_rows, void* stream);
+/* ------------------------------------------------------------------------
+ * Inner-product PNN (test_model/PNN.py:78-83, use_inner) on the first layer of the dnn_* tower:
+ * over the F embedded fields of x0 [B, ld], field f in columns [x_col0 + f E, x_col0 + (f + 1) E),
+ * with theta [D1][F] (row-major, the variable product-quadratic-inner):
+ *   T_i = sum_f theta[i][f] e_f;  lp_i = sqrt(sum_e T_i[e]^2)
+ * 2 <= F <= 64, E one of 8, 16, 32, D1 >= 1; anything else is refused and nothing is written.
+ * T is formed per sample on v_mfma_f32_16x16x4_f32 (exact f32, a k-ordered fma chain over the
+ * fields) and never goes to HBM.
+ * dl_pnn_inner_fwd finishes the layer in place: C [B, ldc] holds the pre-activation x0 W_0 + b_0
+ * (the first layer's GEMM with epi 0) and becomes relu(C + lp) in columns [0, D1); with bits != NULL
+ * the ReLU sign record is written in dl_gemm_s3_nt_bits' layout (bit c & 15 of halfword
+ * bits[b * ldbits + (c >> 4)] = (C + lp > 0), zero bits past D1 in the last halfword;
+ * ldbits >= ceil(D1 / 16)).
+ * dl_pnn_inner_bwd recomputes T and lp and, with d [B, ldd] = dL/d(pre-activation) (the
+ * ReluGrad-masked dh[0]) and dT_i = d_i T_i / lp_i (0 where lp_i == 0: tf.norm's NaN gradient at 0
+ * is not reproduced), adds de_f = sum_i theta[i][f] dT_i INTO dx0 [B, dx_ld] columns
+ * [dx_col0, dx_col0 + F E) and leaves dtheta[i][f] = sum_b sum_e dT_i[e] e_f[e] as per-block
+ * partials slab[block][D1 F] in theta's layout (dl_pnn_grid(B) blocks, at most 512; dl_adam_dense
+ * sums them in slab order).  No atomics: the same inputs give the same bits on every run. */
+int dl_pnn_grid(int32_t B);
+int dl_pnn_inner_fwd(int32_t B, int32_t F, int32_t E, int32_t D1, const float* x0, int32_t ld, int32_t x_col0,
+                     const float* theta, float* C, int32_t ldc, uint16_t* bits, int32_t ldbits, void* stream);
+int dl_pnn_inner_bwd(int32_t B, int32_t F, int32_t E, int32_t D1, const float* x0, int32_t ld, int32_t x_col0,
+                     const float* theta, const float* d, int32_t ldd, float* dx0, int32_t dx_ld, int32_t dx_col0,
+                     float* slab, int32_t slab_rows, void* stream);
 /* The f32 vector-rate yardstick of scripts/afm_bench.py: `blocks` blocks of 256 threads, each thread
  * 16 independent chains of `iters` FMAs (32 * iters FLOP a thread, no memory traffic); out needs
  * blocks * 256 floats (n_out is checked). */

@@ -157,6 +157,13 @@ SIGNATURES = {
     "dl_pnn_grid": (I32, [I32]),
     "dl_pnn_inner_fwd": (I32, [I32, I32, I32, I32, P, I32, I32, P, P, I32, P, I32, P]),
     "dl_pnn_inner_bwd": (I32, [I32, I32, I32, I32, P, I32, I32, P, P, I32, P, I32, I32, P, I32, P]),
+    "dl_bn_grid": (I32, [I32]),
+    "dl_bn_zero_bias_grad": (I32, [P, I32, I64, I64, I32, P]),
+    "dl_bn_ws_floats": (I64, [I32, I32]),
+    "dl_bn_stats": (I32, [I32, I32, P, I32, F, F, P, P, P, P, P, I64, P]),
+    "dl_bn_fwd": (I32, [I32, I32, P, I32, P, P, P, F, P, P, I32, P, I32, P]),
+    "dl_bn_bwd_sums": (I32, [I32, I32, P, I32, P, I32, P, I32, P]),
+    "dl_bn_bwd_apply": (I32, [I32, I32, P, I32, P, I32, P, P, P, I32, P, P]),
     "dl_loss_accumulate_weighted":(I32, [P, I32, I32, I32, P, P, F, P, P, P]),
     "dl_slab_fold_rows": (I32, [P, I32, I32, I32, I32, P, I64, P, P]),
     "dl_adam_begin_step": (I32, [P, F, F, P]),

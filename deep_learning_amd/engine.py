@@ -95,6 +95,12 @@ class ModelSpec:
     0's pre-activation before its ReLU (hidden[0] = D1); parameter product-quadratic-inner [D1, F],
     no regulariser; the reference's product-linear and product-bias are layer 0 itself; None: off
     (DESIGN 4m).
+    batch_norm: batch normalisation (test_model/NFM.py:160-167, 244-252: nn.BatchNorm1d, torch's
+    defaults bn_eps = 1e-5, bn_momentum = 0.1) between every hidden layer's linear part and its ReLU,
+    for every model with an f32 tower: training steps normalise by the batch's unweighted statistics
+    and update the running ones, predict uses the running ones; per hidden layer l the parameters
+    batch_norm_{l+1}.weight / .bias [D] (Adam, no regulariser) and the state batch_norm_{l+1}.running_mean
+    / .running_var [D]; False: none.
     wide_optimizer: "adam" (the reference's one optimizer) or "ftrl" (wdl only): wdl_weights trained
     by TF1 FtrlOptimizer(wide_lr, learning_rate_power=-0.5, initial_accumulator_value=0.1,
     l1_regularization_strength=wide_l1, l2_regularization_strength=wide_l2), the loss's L2 term on
@@ -110,7 +116,7 @@ class ModelSpec:
                  multi_ranges=(), Fw=0, lr=0.001, l2=1e-5, decay_steps=10000000, decay_rate=0.9,
                  beta1=0.9, beta2=0.999, eps=1e-8, logloss_eps=1e-7, tower="f32", dropout_keep_deep=None,
                  dropout_keep_fm=None, pos_weight=1.0, cross_layers=0, wide_optimizer="adam", wide_lr=None,
-                 wide_l1=0.0, wide_l2=0.0, afm_attention=0, pnn=None):
+                 wide_l1=0.0, wide_l2=0.0, afm_attention=0, pnn=None, batch_norm=False, bn_eps=1e-5, bn_momentum=0.1):
         if model not in FAMILIES:
             raise ValueError("unsupported model %r" % model)
         if wide_optimizer not in ("adam", "ftrl"):
@@ -137,6 +143,12 @@ class ModelSpec:
         if pnn not in (None, "inner"):
             raise ValueError("pnn must be None or 'inner', got %r" % (pnn,))
         self.pnn = pnn
+        self.batch_norm = bool(batch_norm)
+        self.bn_eps, self.bn_momentum = float(bn_eps), float(bn_momentum)
+        if not (math.isfinite(self.bn_eps) and self.bn_eps > 0.0):
+            raise ValueError("batch_norm: bn_eps must be finite and > 0, got %r" % (bn_eps,))
+        if not 0.0 < self.bn_momentum <= 1.0:
+            raise ValueError("batch_norm: bn_momentum must lie in (0, 1], got %r" % (bn_momentum,))
         pos_weight = float(pos_weight)
         if not (math.isfinite(pos_weight) and pos_weight > 0.0):
             raise ValueError("pos_weight must be finite and > 0, got %r" % (pos_weight,))
@@ -224,6 +236,18 @@ class ModelSpec:
                 raise ValueError("pnn: 2 to %d embedded fields of size %s, got %d fields of size %d"
                                  % (self.PNN_MAX_FIELDS, " / ".join(map(str, self.PNN_EMB)), self.afm_fields,
                                     self.E))
+
+        if self.batch_norm:
+            if tower == "bf16":
+                raise ValueError("batch_norm: not supported with tower='bf16' (the normalisation finishes the "
+                                 "f32 tower's stored pre-activations)")
+            if self.dropout and any(k < 1.0 for k in self.dropout[1:]):
+                raise ValueError("batch_norm: not supported with dropout on a hidden layer's output "
+                                 "(dropout_keep_deep[l + 1] < 1: that layer's ReLU and dropout live in the GEMM "
+                                 "epilogue the normalisation replaces)")
+            if self.pnn:
+                raise ValueError("batch_norm: not supported together with pnn (both finish layer 0's stored "
+                                 "pre-activation in place)")
 
     @property
     def afm_fields(self):
@@ -637,6 +661,30 @@ class CTREngine:
             self.pm, self.pv = torch.zeros_like(self.pw), torch.zeros_like(self.pw)
             self.pnn_blocks = call_int("dl_pnn_grid", B)
             self.pnn_slab = z(self.pnn_blocks, self.pnn_n)
+        # batch normalisation (ModelSpec.batch_norm, csrc/bn.hip), per hidden layer: [gamma | beta] with
+        # its Adam moments, [running_mean | running_var], the step's [mu_hi | mu_lo | invstd], xhat
+        # [B, h_ld] and the backward's per-block partial sums; the statistics' partials and the merged
+        # backward sums are consumed at once and shared by the layers
+        self.bn = sp.batch_norm
+        if self.bn:
+            if type(self) is not CTREngine:
+                raise ValueError("batch_norm: not supported by %s (the batch statistics would need a reduction "
+                                 "across the ranks)" % type(self).__name__)
+            self.bn_blocks = call_int("dl_bn_grid", B)
+            dp = [_ru(h, 16) for h in sp.hidden]
+            self.bn_w = [z(_ru(2 * h, 4)) for h in sp.hidden]
+            for w, h in zip(self.bn_w, sp.hidden):
+                w[:h] = 1.0
+            self.bn_m = [torch.zeros_like(w) for w in self.bn_w]
+            self.bn_v = [torch.zeros_like(w) for w in self.bn_w]
+            self.bn_run = [z(2, h) for h in sp.hidden]
+            for r in self.bn_run:
+                r[1] = 1.0
+            self.bn_stat = [z(3 * d) for d in dp]
+            self.hx = [z(B, self.h_ld[l]) for l in range(len(sp.hidden))]
+            self.bn_slab = [z(self.bn_blocks, 2 * h) for h in sp.hidden]
+            self.bn_ws = z(max(call_int("dl_bn_ws_floats", B, h) for h in sp.hidden))
+            self.bn_sums = z(2 * max(dp))
         self.head_grid ="dl_wdl_head_grid" if self.wdl else "dl_head_grid"   # slab rows per batch size
         self.head_blocks = call_int(self.head_grid, B)
         self.head_slab = z(self.head_blocks, sp.fm_cols + H + 2)
@@ -856,6 +904,8 @@ class CTREngine:
                 self.first[:N].copy_(first)
         for l in range(len(sp.hidden)):
             self._set_layer(l, P["deep_%d" % l], P["deep_bias_%d" % l])
+        if self.bn:
+            self._bn_load(P)
         if self.wdl:
             self.ww.zero_()
             self.ww[: self.w_rows].copy_(torch.from_numpy(np.ascontiguousarray(P["wdl_weights"][:, 0], np.float32)))
@@ -883,6 +933,35 @@ class CTREngine:
         if self.pnn:
             self.pw[: self.pnn_n].copy_(torch.from_numpy(self._pnn_pack(P)))
         torch.cuda.synchronize()
+
+    BN_KEY = "batch_norm_%d.%s"   # NFM.py:166: setattr(self, 'batch_norm_' + str(i), ...), i from 1
+
+    def _bn_load(self, P):
+        """Reference-layout gamma, beta and running statistics of every hidden layer -> the device
+        (absent running statistics: torch's initial 0 and 1)."""
+        for l, D in enumerate(self.spec.hidden):
+            def get(part, default=None):
+                k = self.BN_KEY % (l + 1, part)
+                if k not in P and default is not None:
+                    return np.full(D, default, np.float32)
+                a = np.ascontiguousarray(P[k], np.float32).reshape(-1)
+                if a.size != D:
+                    raise ValueError("%s holds %d values for %d units" % (k, a.size, D))
+                return a
+            self.bn_w[l][: 2 * D].copy_(torch.from_numpy(np.concatenate([get("weight"), get("bias")])))
+            self.bn_run[l].copy_(torch.from_numpy(np.stack([get("running_mean", 0.0), get("running_var", 1.0)])))
+
+    def _bn_unpack(self, vecs, run=None):
+        """Per-layer [gamma | beta] vectors (and [running_mean | running_var]) -> reference keys."""
+        out = {}
+        for l, D in enumerate(self.spec.hidden):
+            v = vecs[l][: 2 * D].cpu().numpy()
+            out[self.BN_KEY % (l + 1, "weight")], out[self.BN_KEY % (l + 1, "bias")] = v[:D].copy(), v[D:].copy()
+            if run is not None:
+                r = run[l].cpu().numpy()
+                out[self.BN_KEY % (l + 1, "running_mean")] = r[0].copy()
+                out[self.BN_KEY % (l + 1, "running_var")] = r[1].copy()
+        return out
 
     PNN_KEY = "product-quadratic-inner"   # PNN.py:57, [D1, F]: the device vector is its row-major image
 
@@ -986,6 +1065,8 @@ class CTREngine:
                                getattr(self, "aw", None), getattr(self, "pw", None))
         if self.ftrl:
             P.update(self._ftrl_export(wz, wn))
+        if self.bn:
+            P.update(self._bn_unpack(self.bn_w, self.bn_run))
         return P
 
     def dense_state(self):
@@ -997,11 +1078,15 @@ class CTREngine:
             d = {"m": self._export_dense(self.Wm, self.hm, None, self.wbm, None),
                  "v": self._export_dense(self.Wv, self.hv, None, self.wbv, None)}
             d.update(self._ftrl_export(wm, wv))
-            return d
-        return {"m": self._export_dense(self.Wm, self.hm, wm, getattr(self, "wbm", None), getattr(self, "cm", None),
-                                        getattr(self, "am", None), getattr(self, "pm", None)),
-                "v": self._export_dense(self.Wv, self.hv, wv, getattr(self, "wbv", None), getattr(self, "cv", None),
-                                        getattr(self, "av", None), getattr(self, "pv", None))}
+        else:
+            d = {"m": self._export_dense(self.Wm, self.hm, wm, getattr(self, "wbm", None), getattr(self, "cm", None),
+                                         getattr(self, "am", None), getattr(self, "pm", None)),
+                 "v": self._export_dense(self.Wv, self.hv, wv, getattr(self, "wbv", None), getattr(self, "cv", None),
+                                         getattr(self, "av", None), getattr(self, "pv", None))}
+        if self.bn:   # gamma's and beta's moments (the running statistics are state, not trained)
+            d["m"].update(self._bn_unpack(self.bn_m))
+            d["v"].update(self._bn_unpack(self.bn_v))
+        return d
 
     # ------------------------------------------------------------------ wide records (wdl)
     FTRL_KEYS = ("ftrl/z", "ftrl/n")   # FTRL's linear and accumulator state of wdl_weights, [N + H, 1]
@@ -1234,6 +1319,8 @@ class CTREngine:
             return False
         if self.cross or self.afm or self.pnn:   # all read x0's deep columns, which the fused forms leave unwritten
             return False
+        if self.bn:   # the fused forms apply the ReLU themselves; layer 0 must store its pre-activation
+            return False
         pl = self.p_plane
         return (pl is not None and self.cat_col == 0 and sp.E in (8, 16, 32, 64) and 0 < sp.S <= 40
                 and (sp.S * sp.E) % 32 == 0 and sp.S * sp.E <= self.in_ld[0]
@@ -1459,6 +1546,10 @@ class CTREngine:
                 epi = 0 if l == 0 and self.pnn else 1
                 if l == 0 and self.pnn:
                     pnn_bits, bits = bits, (None, 0)
+                # batch normalisation: every layer stores its pre-activation; _bn_fwd normalises it and
+                # applies the ReLU (and writes the sign bitmask) in place
+                if self.bn:
+                    epi, bn_bits, bits = 0, bits, (None, 0)
                 if l == 0 and fused == "rows":
                     # the training form: rows_u through the inverse map (deep slots after the FM
                     # slots), x0's deep columns written for the weight gradient
@@ -1491,16 +1582,53 @@ class CTREngine:
                             self.h_ld[l], epi, None, 0, *bits, s)
                 if l == 0 and self.pnn:
                     self._pnn_fwd(B, pnn_bits, s)
+                if self.bn:
+                    self._bn_fwd(l, B, bn_bits, train, s)
                 x = self.h[l]
         else:
             x = self.x0
             for l, hdim in enumerate(sp.hidden):
                 self._c("gemm_fwd_l%d" % l, "dl_gemm_f32", 0, 0, B, hdim, self.in_ld[l], ptr(x), self.in_ld[l],
                         ptr(self.W[l]), self.out_ld[l], ptr(self.h[l]), self.h_ld[l],
-                        0 if l == 0 and self.pnn else 1, None, 0, 1, 0, s)
+                        0 if (l == 0 and self.pnn) or self.bn else 1, None, 0, 1, 0, s)
                 if l == 0 and self.pnn:   # (the f32 path reads the ReLU's sign from h[0] itself)
                     self._pnn_fwd(B, (None, 0), s)
+                if self.bn:
+                    self._bn_fwd(l, B, (None, 0), train, s)
                 x = self.h[l]
+
+    def _bn_fwd(self, l, B, bits, train, s):
+        """h[l] = relu(gamma xhat + beta) on layer l's stored pre-activation: a training step takes the
+        batch's statistics (kept in bn_stat[l], xhat in hx[l], for the backward) and updates the running
+        ones under the step guard; predict normalises by the running ones."""
+        sp = self.spec
+        D, run = sp.hidden[l], self.bn_run[l]
+        if train:
+            self._c("bn_stats_l%d" % l, "dl_bn_stats", B, D, ptr(self.h[l]), self.h_ld[l], sp.bn_eps, sp.bn_momentum,
+                    ptr(self.bn_stat[l]), ptr(run[0]), ptr(run[1]), ptr(self.opt), ptr(self.bn_ws),
+                    self.bn_ws.numel(), s)
+            self._c("bn_fwd_l%d" % l, "dl_bn_fwd", B, D, ptr(self.h[l]), self.h_ld[l], ptr(self.bn_stat[l]), None,
+                    None, sp.bn_eps, ptr(self.bn_w[l]), ptr(self.hx[l]), self.h_ld[l], *bits, s)
+        else:
+            self._c("bn_fwd_l%d" % l, "dl_bn_fwd", B, D, ptr(self.h[l]), self.h_ld[l], None, ptr(run[0]),
+                    ptr(run[1]), sp.bn_eps, ptr(self.bn_w[l]), None, 0, *bits, s)
+
+    def _bn_bwd(self, l, B, s):
+        """Layer l's batch-norm backward on the ReluGrad-masked dh[l]: dgamma / dbeta as slab rows for
+        the layer's Adam, then dh[l] rewritten in place into the gradient of the pre-activation."""
+        D = self.spec.hidden[l]
+        nb = call_int("dl_bn_grid", B)
+        self._c("bn_sums_l%d" % l, "dl_bn_bwd_sums", B, D, ptr(self.dh[l]), self.h_ld[l], ptr(self.hx[l]),
+                self.h_ld[l], ptr(self.bn_slab[l]), nb, s)
+        self._c("bn_apply_l%d" % l, "dl_bn_bwd_apply", B, D, ptr(self.dh[l]), self.h_ld[l], ptr(self.hx[l]),
+                self.h_ld[l], ptr(self.bn_w[l]), ptr(self.bn_stat[l]), ptr(self.bn_slab[l]), nb, ptr(self.bn_sums), s)
+
+    def _bn_adam(self, B, s):
+        """gamma / beta's Adam, a layer at a time from its slab rows: no regulariser."""
+        nb = call_int("dl_bn_grid", B)
+        for l, D in enumerate(self.spec.hidden):
+            self._c("adam_bn_l%d" % l, "dl_adam_dense", ptr(self.bn_w[l]), ptr(self.bn_m[l]), ptr(self.bn_v[l]),
+                    ptr(self.bn_slab[l]), nb, 2 * D, 2 * D, 0.0, 0, ptr(self.opt), None, None, s)
 
     def _pnn_fwd(self, B, bits, s):
         """h[0] = relu(h[0] + lp): the product layer on layer 0's stored pre-activation (x0 is complete:
@@ -1638,7 +1766,14 @@ class CTREngine:
             # fused: every layer's weight and input gradients, then one launch for the dense Adams
             # (each layer's W planes are read by its dX first; nothing else reads W before the next
             # step); else each layer's Adam after its input gradient
+            if self.bn:   # dh[l] becomes the pre-activation's gradient before the layer's GEMMs read it
+                self._bn_bwd(l, B, s)
             self._tower_dw(l, B, dws[l], self.w_slabs[l], s)
+            if self.bn:
+                # the layer's own bias: its exact gradient, 0, in place of the weight gradient's noise row
+                self._c("bn_bias_l%d" % l, "dl_bn_zero_bias_grad", ptr(self.w_slabs[l]),
+                        _num_splits(B, dws[l], 64 if (self.bf or self.s3) else 16), self.in_ld[l] * self.out_ld[l],
+                        ([self.D0] + sp.hidden)[l] * self.out_ld[l], self.out_ld[l], s)
             self._tower_dx(l, B, s)
             if not fused:
                 self._tower_adam(l, self.w_slabs[l], _num_splits(B, dws[l], 64 if (self.bf or self.s3) else 16), s)
@@ -1811,6 +1946,8 @@ class CTREngine:
                  ptr(self.touched), *fd, s)
         H = sp.hidden[-1]
         hb = call_int(self.head_grid, B)
+        if self.bn:   # (before the families part ways: wdl has gamma and beta too)
+            self._bn_adam(B, s)
         if self.wdl and self.wide_lazy:
             # wdl_weights, lazy: the deep-output rows' batch sums folded into the local gradient,
             # then TF1 Adam (L2 on every row, wdl.py:270-271) on the batch's unique wide rows and
@@ -1975,6 +2112,9 @@ class CTREngine:
     def train_step(self, batch=None, graph=False, next_batch=None):
         """One training step on `batch` (or on the already-staged slots if None).
         next_batch: prefetch it (stage + index build on the side stream) during this step."""
+        if self.bn and (self.B if batch is None else int(np.prod(np.shape(batch["label"])))) < 2:
+            raise ValueError("batch_norm: a training batch needs at least 2 samples (the batch variance and its "
+                             "unbiased factor B / (B - 1) are undefined at B = 1)")
         B, indexed = self._begin(batch)
         if self.p_plane is not None:   # predict's planes go stale: free them
             self.p_plane = self.w1_plane = None

@@ -22,6 +22,9 @@ test_model/AFM.py over the embedded fields, A attention units, its logit added t
 pnn=inner (the same four models) puts the inner-product layer of the reference's test_model/PNN.py in
 front of the tower: the norm of a learned mix of the embedded fields, per unit of the first hidden layer.
 
+batch_norm=1 bn_eps=1e-5 bn_momentum=0.1 (every model) normalises each hidden layer's pre-activation
+over the batch before its ReLU (the reference's test_model/NFM.py); predict uses the running statistics.
+
 wide_optimizer=ftrl wide_lr=0.05 wide_l1=1e-3 wide_l2=0 (wdl: models/wdl.py reads them from its args)
 train the wide weights with FTRL-proximal instead of Adam; L1 leaves most wide rows at exactly zero.
 
@@ -91,6 +94,8 @@ class ModelParams:
                 self.afm_attention = check_afm_attention(v, self.alg_name)
             elif k == "pnn":             # the product layer in front of the tower, likewise
                 self.pnn = check_pnn(v, self.alg_name)
+            elif k in ("batch_norm", "bn_eps", "bn_momentum"):   # batch normalisation in the tower, likewise
+                setattr(self, k, check_batch_norm(k, v))
             elif k in ("wide_optimizer", "wide_lr", "wide_l1", "wide_l2"):   # stored only when given, too
                 setattr(self, k, check_wide_option(k, v, self.alg_name))
             else:
@@ -157,6 +162,22 @@ def check_pnn(v, alg_name):
         raise SystemExit("pnn=%s: the product layer feeds the tower of %s only, not %s"
                          % (v, ", ".join(ModelSpec.CROSS_MODELS), alg_name))
     return v
+
+
+def check_batch_norm(k, v):
+    """batch_norm=0|1 as a bool, bn_eps / bn_momentum as floats; refuses (SystemExit) what ModelSpec
+    would: bn_eps <= 0, bn_momentum outside (0, 1], anything not finite."""
+    if k == "batch_norm":
+        if v not in ("0", "1"):
+            raise SystemExit("batch_norm=%s must be 0 or 1" % v)
+        return v == "1"
+    try:
+        x = float(v)
+    except ValueError:
+        raise SystemExit("%s=%s is not a number" % (k, v))
+    if not (0.0 < x < float("inf")) or (k == "bn_momentum" and x > 1.0):
+        raise SystemExit("%s=%s must %s" % (k, v, "lie in (0, 1]" if k == "bn_momentum" else "be finite and > 0"))
+    return x
 
 
 def check_wide_option(k, v, alg_name):

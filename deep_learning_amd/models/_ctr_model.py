@@ -58,6 +58,9 @@ def _spec_from_args(model, args):
         kw.update(afm_attention=int(args.afm_attention))
     if getattr(args, "pnn", None) is not None:             # local_run's pnn= (stored only when given)
         kw.update(pnn=args.pnn)
+    for k in ("batch_norm", "bn_eps", "bn_momentum"):      # local_run's batch_norm= bn_eps= bn_momentum=, likewise
+        if getattr(args, k, None) is not None:
+            kw[k] = getattr(args, k)
     return ModelSpec(model, **kw)
 
 
@@ -239,6 +242,9 @@ def _adam_state(eng):
         out["adam/am"], out["adam/av"] = eng.am.cpu().numpy(), eng.av.cpu().numpy()
     if eng.pnn:     # theta's moments, row-major [D1, F] as the device vector (engine.py _pnn_pack)
         out["adam/pm"], out["adam/pv"] = eng.pm.cpu().numpy(), eng.pv.cpu().numpy()
+    if eng.bn:      # gamma's and beta's moments per hidden layer, [gamma | beta] as the device vector
+        for l in range(len(eng.W)):
+            out["adam/bn_m%d" % l], out["adam/bn_v%d" % l] = eng.bn_m[l].cpu().numpy(), eng.bn_v[l].cpu().numpy()
     for l in range(len(eng.W)):
         out["adam/Wm%d" % l] = eng.Wm[l].cpu().numpy()
         out["adam/Wv%d" % l] = eng.Wv[l].cpu().numpy()
@@ -265,6 +271,10 @@ def _load_adam_state(eng, d):
     if eng.pnn:
         eng.pm.copy_(torch.from_numpy(d["adam/pm"]))
         eng.pv.copy_(torch.from_numpy(d["adam/pv"]))
+    if eng.bn:
+        for l in range(len(eng.W)):
+            eng.bn_m[l].copy_(torch.from_numpy(d["adam/bn_m%d" % l]))
+            eng.bn_v[l].copy_(torch.from_numpy(d["adam/bn_v%d" % l]))
     for l in range(len(eng.W)):
         eng.Wm[l].copy_(torch.from_numpy(d["adam/Wm%d" % l]))
         eng.Wv[l].copy_(torch.from_numpy(d["adam/Wv%d" % l]))

@@ -188,6 +188,9 @@ class ShardedCTREngine(CTREngine):
         if spec.pnn:
             raise ValueError("pnn: not supported by ShardedCTREngine (theta's gradient is not part of the flat "
                              "all-reduce)")
+        if spec.batch_norm:
+            raise ValueError("batch_norm: not supported by ShardedCTREngine (the batch statistics would need a "
+                             "reduction across the ranks)")
         # the status ring holds 4 reports (slot k & 3) and the host reads report k only after
         # k + lag was submitted: lag <= 3, or report k + 4 overwrites k before it is read
         if not 0 <= int(lag) <= 3:

@@ -539,6 +539,51 @@ int dl_pnn_inner_fwd(int32_t B, int32_t F, int32_t E, int32_t D1, const float* x
 int dl_pnn_inner_bwd(int32_t B, int32_t F, int32_t E, int32_t D1, const float* x0, int32_t ld, int32_t x_col0,
                      const float* theta, const float* d, int32_t ldd, float* dx0, int32_t dx_ld, int32_t dx_col0,
                      float* slab, int32_t slab_rows, void* stream);
+/* ------------------------------------------------------------------------
+ * Batch normalisation of a hidden layer (test_model/NFM.py:160-167, 244-252: nn.BatchNorm1d after
+ * linear_i, before the activation) on the tower's stored pre-activation C [B, ldc] (the layer's
+ * GEMM with epi 0), columns [0, D):
+ *   mu_j = mean_b C[b][j];  var_j = mean_b (C[b][j] - mu_j)^2;  xhat = (C - mu) / sqrt(var + eps)
+ *   y = gamma xhat + beta;  h = relu(y)
+ * params [2 D] = [gamma | beta] (the layer's Adam vector).  With Dp = 16 ceil(D / 16):
+ * stat [3 Dp] = [mu_hi | mu_lo | 1 / sqrt(var + eps)] (mu = mu_hi + mu_lo, so C - mu keeps f32
+ * accuracy at any offset), sums [2 Dp] = [dgamma | dbeta].  ldc, ldx, ldd are multiples of 4 and
+ * >= D, every matrix 16-B aligned; D < 1, a pitch below D and (statistics, backward) B < 2 are
+ * refused and nothing is written.  Columns past D keep their bits.
+ * dl_bn_grid(B): the row blocks of every kernel here (at most 1024, at least 32 rows each) = the
+ * slab rows of the backward.
+ * dl_bn_stats: per block the shifted sums (K = the block's first row; sum (c - K), sum (c - K)^2),
+ * i.e. the block's (n, mean, M2), merged in block order in float64 by Chan's formula (never
+ * E[c^2] - mu^2) into stat; with run_mean != NULL, and unless opt's step is poisoned
+ * (dl_step_begin), running_mean <- (1 - m) running_mean + m mu and running_var <- (1 - m)
+ * running_var + m var B / (B - 1).  ws: dl_bn_ws_floats(B, D) floats.
+ * dl_bn_fwd finishes the layer in place: C becomes relu(gamma xhat + beta); with stat != NULL
+ * (training) xhat comes from stat and is written to hx [B, ldx]; with stat == NULL (inference)
+ * from run_mean / run_var / eps, and hx must be NULL.  With bits != NULL the ReLU sign record is
+ * written in dl_gemm_s3_nt_bits' layout (bit c & 15 of halfword bits[b * ldbits + (c >> 4)] =
+ * (y > 0), zero bits past D in the last halfword; ldbits >= ceil(D / 16)).
+ * dl_bn_bwd_sums, dy [B, ldd] = dL/dy (the ReluGrad-masked dh): slab[block][2 D] = the block's
+ * [sum_b dy xhat | sum_b dy], params' layout (dl_adam_dense sums the rows in slab order).
+ * dl_bn_bwd_apply merges the slab's rows in order into sums and rewrites dy in place into
+ *   dc = gamma / sqrt(var + eps) (dy - dbeta / B - xhat dgamma / B).
+ * dl_bn_zero_bias_grad: the layer's own bias has dL/db = sum_b dc = 0 identically under batch norm;
+ * the weight gradient's bias row (cols floats at `offset` of each of nslab split-K slabs, `stride`
+ * floats apart) holds that sum's f32 rounding noise, which Adam would normalise into steps of the
+ * order of lr, and is set to the exact 0.
+ * No atomics, no memset: the same inputs give the same bits on every run. */
+int dl_bn_zero_bias_grad(float* slab, int32_t nslab, int64_t stride, int64_t offset, int32_t cols, void* stream);
+int dl_bn_grid(int32_t B);
+int64_t dl_bn_ws_floats(int32_t B, int32_t D);
+int dl_bn_stats(int32_t B, int32_t D, const float* C, int32_t ldc, float eps, float momentum, float* stat,
+                float* run_mean, float* run_var, const float* opt, float* ws, int64_t ws_floats, void* stream);
+int dl_bn_fwd(int32_t B, int32_t D, float* C, int32_t ldc, const float* stat, const float* run_mean,
+              const float* run_var, float eps, const float* params, float* hx, int32_t ldx, uint16_t* bits,
+              int32_t ldbits, void* stream);
+int dl_bn_bwd_sums(int32_t B, int32_t D, const float* dy, int32_t ldd, const float* hx, int32_t ldx, float* slab,
+                   int32_t slab_rows, void* stream);
+int dl_bn_bwd_apply(int32_t B, int32_t D, float* dy, int32_t ldd, const float* hx, int32_t ldx,
+                    const float* params, const float* stat, const float* slab, int32_t slab_rows, float* sums,
+                    void* stream);
 /* The f32 vector-rate yardstick of scripts/afm_bench.py: `blocks` blocks of 256 threads, each thread
  * 16 independent chains of `iters` FMAs (32 * iters FLOP a thread, no memory traffic); out needs
  * blocks * 256 floats (n_out is checked). */

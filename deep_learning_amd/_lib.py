@@ -157,6 +157,9 @@ SIGNATURES = {
     "dl_pnn_grid": (I32, [I32]),
     "dl_pnn_inner_fwd": (I32, [I32, I32, I32, I32, P, I32, I32, P, P, I32, P, I32, P]),
     "dl_pnn_inner_bwd": (I32, [I32, I32, I32, I32, P, I32, I32, P, P, I32, P, I32, I32, P, I32, P]),
+    "dl_bi_grid": (I32, [I32]),
+    "dl_bi_fwd": (I32, [I32, I32, I32, P, I32, I32, P, I32, I32, P]),
+    "dl_bi_bwd": (I32, [I32, I32, I32, P, I32, I32, P, I32, I32, P, I32, I32, P]),
     "dl_bn_grid": (I32, [I32]),
     "dl_bn_zero_bias_grad": (I32, [P, I32, I64, I64, I32, P]),
     "dl_bn_ws_floats": (I64, [I32, I32]),

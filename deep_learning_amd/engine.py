@@ -101,6 +101,10 @@ class ModelSpec:
     and update the running ones, predict uses the running ones; per hidden layer l the parameters
     batch_norm_{l+1}.weight / .bias [D] (Adam, no regulariser) and the state batch_norm_{l+1}.running_mean
     / .running_var [D]; False: none.
+    bi_interaction: True adds the Bi-Interaction pooling of test_model/NFM.py:192-197, 226 to the same four
+    models' tower input: q = sum_{f<g} e_f * e_g over the S + M embedded fields, E more columns after the
+    reference's [cont, vector, single cate, pooled] (deep_0 becomes [deep_in, hidden[0]] with deep_in
+    grown by E); no new parameter; with batch_norm=True the reference's NFM; False: none.
     wide_optimizer: "adam" (the reference's one optimizer) or "ftrl" (wdl only): wdl_weights trained
     by TF1 FtrlOptimizer(wide_lr, learning_rate_power=-0.5, initial_accumulator_value=0.1,
     l1_regularization_strength=wide_l1, l2_regularization_strength=wide_l2), the loss's L2 term on
@@ -111,12 +115,14 @@ class ModelSpec:
     CROSS_MAX_LAYERS, CROSS_MAX_IN = 4, 1024     # csrc/cross.hip
     AFM_MAX_ATT, AFM_MAX_FIELDS, AFM_EMB = 32, 64, (8, 16, 32)     # csrc/afm.hip
     PNN_MAX_FIELDS, PNN_EMB = 64, (8, 16, 32)                      # csrc/pnn.hip
+    BI_MAX_FIELDS, BI_MAX_EMB = 64, 64                             # csrc/bi.hip (E a multiple of 4)
 
     def __init__(self, model, C=13, V=0, S=26, E=16, cate_index_size=1000, hidden=(400, 400, 400),
                  multi_ranges=(), Fw=0, lr=0.001, l2=1e-5, decay_steps=10000000, decay_rate=0.9,
                  beta1=0.9, beta2=0.999, eps=1e-8, logloss_eps=1e-7, tower="f32", dropout_keep_deep=None,
                  dropout_keep_fm=None, pos_weight=1.0, cross_layers=0, wide_optimizer="adam", wide_lr=None,
-                 wide_l1=0.0, wide_l2=0.0, afm_attention=0, pnn=None, batch_norm=False, bn_eps=1e-5, bn_momentum=0.1):
+                 wide_l1=0.0, wide_l2=0.0, afm_attention=0, pnn=None, batch_norm=False, bn_eps=1e-5, bn_momentum=0.1,
+                 bi_interaction=False):
         if model not in FAMILIES:
             raise ValueError("unsupported model %r" % model)
         if wide_optimizer not in ("adam", "ftrl"):
@@ -144,6 +150,7 @@ class ModelSpec:
             raise ValueError("pnn must be None or 'inner', got %r" % (pnn,))
         self.pnn = pnn
         self.batch_norm = bool(batch_norm)
+        self.bi_interaction = bool(bi_interaction)
         self.bn_eps, self.bn_momentum = float(bn_eps), float(bn_momentum)
         if not (math.isfinite(self.bn_eps) and self.bn_eps > 0.0):
             raise ValueError("batch_norm: bn_eps must be finite and > 0, got %r" % (bn_eps,))
@@ -249,10 +256,26 @@ class ModelSpec:
                 raise ValueError("batch_norm: not supported together with pnn (both finish layer 0's stored "
                                  "pre-activation in place)")
 
+        if self.bi_interaction:
+            if model not in self.CROSS_MODELS:
+                raise ValueError("bi_interaction: the Bi-Interaction pooling feeds the tower of %s only, not %s"
+                                 % (", ".join(self.CROSS_MODELS), model))
+            if tower == "bf16":
+                raise ValueError("bi_interaction: not supported with tower='bf16' (the pooling reads and extends "
+                                 "the f32 tower input)")
+            if self.dropout and self.dropout[0] < 1.0:
+                raise ValueError("bi_interaction: not supported with tower-input dropout (dropout_keep_deep[0] < 1 "
+                                 "rewrites x0 in place; the pooling's backward reads the undropped fields)")
+            if (not 2 <= self.afm_fields <= self.BI_MAX_FIELDS or self.E % 4
+                    or not 4 <= self.E <= self.BI_MAX_EMB):
+                raise ValueError("bi_interaction: 2 to %d embedded fields of a size that is a multiple of 4 in "
+                                 "[4, %d], got %d fields of size %d"
+                                 % (self.BI_MAX_FIELDS, self.BI_MAX_EMB, self.afm_fields, self.E))
+
     @property
     def afm_fields(self):
-        """The fields the attentional interactions pair (and the product layer mixes): single-valued,
-        then pooled slots."""
+        """The fields the attentional interactions pair (and the product layer mixes, and the
+        Bi-Interaction pools): single-valued, then pooled slots."""
         return self.S + self.M
 
     @property
@@ -350,7 +373,7 @@ class ModelSpec:
 
     @property
     def deep_in(self):
-        return self.S * self.E + self.M * self.E + self.C + self.V
+        return self.S * self.E + self.M * self.E + self.C + self.V + (self.E if self.bi_interaction else 0)
 
     @property
     def F(self):
@@ -367,6 +390,16 @@ class ModelSpec:
     def cate_ld(self):
         return self.S + self.multi_width
 
+    def check_deep0(self, P):
+        """Refuses reference-layout parameters whose deep_0 has another input width: the one shape
+        bi_interaction changes, so parameters of the other setting do not load."""
+        rows = np.shape(P["deep_0"])[0]
+        if rows != self.deep_in:
+            raise ValueError("deep_0 has %d rows for %d tower-input columns: with bi_interaction=%s the tower "
+                             "input %s the %d Bi-Interaction columns, and parameters of the other setting do "
+                             "not load" % (rows, self.deep_in, self.bi_interaction,
+                                           "holds" if self.bi_interaction else "does not hold", self.E))
+
     def x0_ref_rows(self):
         """Reference row of W_0 for each internal x0 column < deep_in.  Every pipeline-style
         model concatenates its deep input as [cont, vector, single cate, pooled]
@@ -377,7 +410,9 @@ class ModelSpec:
         pool = np.arange(M * E) + C + V + S * E
         cont = np.arange(C)
         vec = np.arange(V) + C
-        return np.concatenate([cat, pool, cont, vec])
+        # bi_interaction: the reference order ends with q; internally q follows the fields it pools
+        bi = np.arange(E if self.bi_interaction else 0) + C + V + (S + M) * E
+        return np.concatenate([cat, pool, bi, cont, vec])
 
 
 
@@ -448,7 +483,14 @@ class CTREngine:
         # ---- layout
         self.cat_col = 0
         self.pool_col = S * E
-        self.cont_col = (S + M) * E
+        # Bi-Interaction pooling (ModelSpec.bi_interaction, csrc/bi.hip): q in the E columns after the
+        # last field, before cont and vector, so [fields | q] is one range of x0 and of dx0 (layer 0's
+        # dX GEMM covers dq by the wider dx_cols); nothing else is allocated
+        self.bi = sp.bi_interaction
+        if self.bi and type(self) is not CTREngine:
+            raise ValueError("bi_interaction: not supported by %s" % type(self).__name__)
+        self.bi_col = (S + M) * E
+        self.cont_col = (S + M) * E + (E if self.bi else 0)
         self.vec_col = self.cont_col + sp.C
         self.D0 = sp.deep_in
         dims = [self.D0] + sp.hidden
@@ -456,7 +498,7 @@ class CTREngine:
         self.out_ld = [_ru(h, 16) for h in sp.hidden]
         self.h_ld = [_ru(h + 1, 16) for h in sp.hidden]
         self.fm_ld = _ru(max(sp.fm_cols, 1), 4)
-        self.dx_cols = (S + M) * E
+        self.dx_cols = (S + M) * E + (E if self.bi else 0)
         self.dx_ld = _ru(max(self.dx_cols, 4), 4)
         # ---- parameters + Adam state
         rows_pad = _ru(table_rows if table_rows is not None else N, 16)
@@ -902,6 +944,7 @@ class CTREngine:
             if self.first is not None:
                 self.first.zero_()
                 self.first[:N].copy_(first)
+        sp.check_deep0(P)
         for l in range(len(sp.hidden)):
             self._set_layer(l, P["deep_%d" % l], P["deep_bias_%d" % l])
         if self.bn:
@@ -1285,6 +1328,8 @@ class CTREngine:
             return False
         if self.drop:   # the plain first layer reads the dropped x0 (and has the dropout epilogue)
             return False
+        if self.bi:     # dl_bi_fwd reads x0's field columns before the first layer runs: the lookup writes them
+            return False
         return (self.cat_col == 0 and sp.E in (8, 16, 32, 64) and 0 < sp.S <= 40 and (sp.S * sp.E) % 32 == 0
                 and sp.S * sp.E <= self.in_ld[0] and self.rows_u.numel() * 4 < 0xFFFFFF00
                 and self.idx_inv is not None)
@@ -1317,7 +1362,7 @@ class CTREngine:
         sp = self.spec
         if os.environ.get("DLAMD_FUSED_GATHER", "1") == "0" or not self.s3 or self.bf or sp.M:
             return False
-        if self.cross or self.afm or self.pnn:   # all read x0's deep columns, which the fused forms leave unwritten
+        if self.cross or self.afm or self.pnn or self.bi:   # all read x0's deep columns, which the fused forms leave unwritten
             return False
         if self.bn:   # the fused forms apply the ReLU themselves; layer 0 must store its pre-activation
             return False
@@ -1454,6 +1499,10 @@ class CTREngine:
             # input dropout on x0's deep_in columns (the bias "ones" column stays); predict never drops
             self._c("drop_x0", "dl_dropout_apply", ptr(self.x0), B, self.D0, self.in_ld[0], *self._drop_args(0),
                     None, s)
+        if self.bi:
+            # q into x0's columns after the fields, from the field columns the lookup has written
+            self._c("bi_fwd", "dl_bi_fwd", B, self.spec.afm_fields, self.spec.E, ptr(self.x0), self.in_ld[0], self.cat_col,
+                    ptr(self.x0), self.in_ld[0], self.bi_col, s)
         self._tower_fwd(B, s, train, fused)
         self._head(B, s, train)
 
@@ -1804,6 +1853,11 @@ class CTREngine:
             self._c("pnn_bwd", "dl_pnn_inner_bwd", B, sp.afm_fields, sp.E, sp.hidden[0], ptr(self.x0), self.in_ld[0],
                     self.cat_col, ptr(self.pw), ptr(self.dh[0]), self.h_ld[0], ptr(self.dx0), self.dx_ld, 0,
                     ptr(self.pnn_slab), self.pnn_blocks, s)
+        if self.bi:
+            # the pooling's share: dq is dx0's columns after the fields (gemm_dx_l0's wider range, plus
+            # the cross network's share of them), complete here
+            self._c("bi_bwd", "dl_bi_bwd", B, sp.afm_fields, sp.E, ptr(self.x0), self.in_ld[0], self.cat_col,
+                    ptr(self.dx0), self.dx_ld, self.bi_col, ptr(self.dx0), self.dx_ld, 0, s)
         self._train_back(B, s, L)
         # the step's loss into the running sum (read once per epoch: loss_sum_end)
         width = self.head_slab.shape[1]

@@ -25,6 +25,10 @@ front of the tower: the norm of a learned mix of the embedded fields, per unit o
 batch_norm=1 bn_eps=1e-5 bn_momentum=0.1 (every model) normalises each hidden layer's pre-activation
 over the batch before its ReLU (the reference's test_model/NFM.py); predict uses the running statistics.
 
+bi_interaction=1 (dnn_pipeline, dnn_cate, dnn_multi, dnn_multi_cate) adds the Bi-Interaction pooling of the
+reference's test_model/NFM.py, the sum of all pairwise products of the embedded fields, as E more columns
+of the tower input; with batch_norm=1 the model is the reference's NFM.
+
 wide_optimizer=ftrl wide_lr=0.05 wide_l1=1e-3 wide_l2=0 (wdl: models/wdl.py reads them from its args)
 train the wide weights with FTRL-proximal instead of Adam; L1 leaves most wide rows at exactly zero.
 
@@ -96,6 +100,8 @@ class ModelParams:
                 self.pnn = check_pnn(v, self.alg_name)
             elif k in ("batch_norm", "bn_eps", "bn_momentum"):   # batch normalisation in the tower, likewise
                 setattr(self, k, check_batch_norm(k, v))
+            elif k == "bi_interaction":   # the Bi-Interaction pooling into the tower input, likewise
+                self.bi_interaction = check_bi_interaction(v, self.alg_name)
             elif k in ("wide_optimizer", "wide_lr", "wide_l1", "wide_l2"):   # stored only when given, too
                 setattr(self, k, check_wide_option(k, v, self.alg_name))
             else:
@@ -162,6 +168,18 @@ def check_pnn(v, alg_name):
         raise SystemExit("pnn=%s: the product layer feeds the tower of %s only, not %s"
                          % (v, ", ".join(ModelSpec.CROSS_MODELS), alg_name))
     return v
+
+
+def check_bi_interaction(v, alg_name):
+    """bi_interaction=0|1 as a bool; refuses (SystemExit) any other value, and bi_interaction=1 for a
+    model other than the dnn_* ones."""
+    from .engine import ModelSpec
+    if v not in ("0", "1"):
+        raise SystemExit("bi_interaction=%s must be 0 or 1" % v)
+    if v == "1" and alg_name not in ModelSpec.CROSS_MODELS:
+        raise SystemExit("bi_interaction=%s: the Bi-Interaction pooling feeds the tower of %s only, not %s"
+                         % (v, ", ".join(ModelSpec.CROSS_MODELS), alg_name))
+    return v == "1"
 
 
 def check_batch_norm(k, v):

@@ -61,6 +61,8 @@ def _spec_from_args(model, args):
     for k in ("batch_norm", "bn_eps", "bn_momentum"):      # local_run's batch_norm= bn_eps= bn_momentum=, likewise
         if getattr(args, k, None) is not None:
             kw[k] = getattr(args, k)
+    if getattr(args, "bi_interaction", None) is not None:  # local_run's bi_interaction= (stored only when given)
+        kw.update(bi_interaction=bool(args.bi_interaction))
     return ModelSpec(model, **kw)
 
 

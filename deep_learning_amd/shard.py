@@ -188,6 +188,9 @@ class ShardedCTREngine(CTREngine):
         if spec.pnn:
             raise ValueError("pnn: not supported by ShardedCTREngine (theta's gradient is not part of the flat "
                              "all-reduce)")
+        if spec.bi_interaction:
+            raise ValueError("bi_interaction: not supported by ShardedCTREngine (its step does not launch the "
+                             "pooling's kernels around the first tower layer)")
         if spec.batch_norm:
             raise ValueError("batch_norm: not supported by ShardedCTREngine (the batch statistics would need a "
                              "reduction across the ranks)")

@@ -584,6 +584,28 @@ int dl_bn_bwd_sums(int32_t B, int32_t D, const float* dy, int32_t ldd, const flo
 int dl_bn_bwd_apply(int32_t B, int32_t D, float* dy, int32_t ldd, const float* hx, int32_t ldx,
                     const float* params, const float* stat, const float* slab, int32_t slab_rows, float* sums,
                     void* stream);
+/* ------------------------------------------------------------------------
+ * Bi-Interaction pooling (test_model/NFM.py:192-197, 226: fm_second_order fed to the deep layers)
+ * over the F embedded fields of x0 [B, ld], field f in columns [x_col0 + f E, x_col0 + (f + 1) E):
+ *   q[e] = sum_{f<g} e_f[e] e_g[e]  ( = 1/2 ((sum_f e_f)^2 - sum_f e_f^2) )
+ * formed as the prefix chain q = sum_f e_f * P_f, P_f = sum_{g<f} e_g: one fma a field in field
+ * order, never the difference of the two large sums.  2 <= F <= 64, E a multiple of 4 in [4, 64],
+ * every column range within its pitch; anything else is refused and nothing is written.
+ * dl_bi_grid(B): the sample blocks of both kernels (at most 1024, at least 32 samples each).
+ * dl_bi_fwd writes q [B, ldq] columns [q_col0, q_col0 + E) and nothing else; q may be x0 itself
+ * (then its columns must miss the fields').
+ * dl_bi_bwd, with dq [B, lddq] columns [dq_col0, dq_col0 + E) = dL/dq and s = sum_g e_g, adds
+ *   de_f = dq * (s - e_f)
+ * INTO dx0 [B, dx_ld] columns [dx_col0, dx_col0 + F E) (the contract of dl_afm_bwd and
+ * dl_pnn_inner_bwd: the three compose in any order) and writes nothing else; dq may be columns of
+ * dx0 itself outside that range.  Accesses are 16 B wide when every pointer, pitch and column
+ * offset is a multiple of 16 B, 4 B wide otherwise, with the same arithmetic.  No parameters, no
+ * workspace, no atomics, no memset: the same inputs give the same bits on every run. */
+int dl_bi_grid(int32_t B);
+int dl_bi_fwd(int32_t B, int32_t F, int32_t E, const float* x0, int32_t ld, int32_t x_col0, float* q, int32_t ldq,
+              int32_t q_col0, void* stream);
+int dl_bi_bwd(int32_t B, int32_t F, int32_t E, const float* x0, int32_t ld, int32_t x_col0, const float* dq,
+              int32_t lddq, int32_t dq_col0, float* dx0, int32_t dx_ld, int32_t dx_col0, void* stream);
 /* The f32 vector-rate yardstick of scripts/afm_bench.py: `blocks` blocks of 256 threads, each thread
  * 16 independent chains of `iters` FMAs (32 * iters FLOP a thread, no memory traffic); out needs
  * blocks * 256 floats (n_out is checked). */

@@ -105,6 +105,11 @@ class ModelSpec:
     models' tower input: q = sum_{f<g} e_f * e_g over the S + M embedded fields, E more columns after the
     reference's [cont, vector, single cate, pooled] (deep_0 becomes [deep_in, hidden[0]] with deep_in
     grown by E); no new parameter; with batch_norm=True the reference's NFM; False: none.
+    ccpm_filters: the channels (C_0, .., C_{L-1}) of a CCPM branch (test_model/CCPM.py:45-68) beside the same
+    four models' tower: L times Conv2D(3x3, same, relu) + MaxPool2D(2x2) on the [E, F] map of the S + M
+    embedded fields, Flatten, Dense(1) without its bias, its logit added to the tower's (after the cross
+    network's and the attentional interactions'); parameters ccpm_conv_{l}.kernel [3, 3, C_{l-1}, C_l],
+    ccpm_conv_{l}.bias [C_l], ccpm_out.kernel [H_L W_L C_L, 1], no regulariser; (): none.
     wide_optimizer: "adam" (the reference's one optimizer) or "ftrl" (wdl only): wdl_weights trained
     by TF1 FtrlOptimizer(wide_lr, learning_rate_power=-0.5, initial_accumulator_value=0.1,
     l1_regularization_strength=wide_l1, l2_regularization_strength=wide_l2), the loss's L2 term on
@@ -116,13 +121,14 @@ class ModelSpec:
     AFM_MAX_ATT, AFM_MAX_FIELDS, AFM_EMB = 32, 64, (8, 16, 32)     # csrc/afm.hip
     PNN_MAX_FIELDS, PNN_EMB = 64, (8, 16, 32)                      # csrc/pnn.hip
     BI_MAX_FIELDS, BI_MAX_EMB = 64, 64                             # csrc/bi.hip (E a multiple of 4)
+    CCPM_MAX_LAYERS, CCPM_MAX_FILTERS, CCPM_MAX_FIELDS, CCPM_EMB = 3, 8, 64, (8, 16, 32)   # csrc/ccpm.hip
 
     def __init__(self, model, C=13, V=0, S=26, E=16, cate_index_size=1000, hidden=(400, 400, 400),
                  multi_ranges=(), Fw=0, lr=0.001, l2=1e-5, decay_steps=10000000, decay_rate=0.9,
                  beta1=0.9, beta2=0.999, eps=1e-8, logloss_eps=1e-7, tower="f32", dropout_keep_deep=None,
                  dropout_keep_fm=None, pos_weight=1.0, cross_layers=0, wide_optimizer="adam", wide_lr=None,
                  wide_l1=0.0, wide_l2=0.0, afm_attention=0, pnn=None, batch_norm=False, bn_eps=1e-5, bn_momentum=0.1,
-                 bi_interaction=False):
+                 bi_interaction=False, ccpm_filters=()):
         if model not in FAMILIES:
             raise ValueError("unsupported model %r" % model)
         if wide_optimizer not in ("adam", "ftrl"):
@@ -143,6 +149,14 @@ class ModelSpec:
         if int(afm_attention) != afm_attention or afm_attention < 0:
             raise ValueError("afm_attention must be an integer >= 0, got %r" % (afm_attention,))
         self.afm_attention = int(afm_attention)
+        try:
+            filters = tuple(ccpm_filters)
+            ok = all(int(c) == c for c in filters)
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise ValueError("ccpm_filters must be a sequence of integers, got %r" % (ccpm_filters,))
+        self.ccpm_filters = tuple(int(c) for c in filters)
         if pnn == "outer":
             raise ValueError("pnn='outer': the outer-product layer (PNN.py:85-91, an E * E first-layer input) is "
                              "not built; pnn='inner' is")
@@ -272,11 +286,38 @@ class ModelSpec:
                                  "[4, %d], got %d fields of size %d"
                                  % (self.BI_MAX_FIELDS, self.BI_MAX_EMB, self.afm_fields, self.E))
 
+        if self.ccpm_filters:
+            if model not in self.CROSS_MODELS:
+                raise ValueError("ccpm_filters: the convolutional interactions join the tower of %s only, not %s"
+                                 % (", ".join(self.CROSS_MODELS), model))
+            if tower == "bf16":
+                raise ValueError("ccpm_filters: not supported with tower='bf16' (the branch reads the f32 "
+                                 "tower input)")
+            if self.dropout and self.dropout[0] < 1.0:
+                raise ValueError("ccpm_filters: not supported with tower-input dropout (dropout_keep_deep[0] < 1 "
+                                 "rewrites x0 in place; the branch reads the undropped fields)")
+            Lc, F = len(self.ccpm_filters), self.afm_fields
+            if (Lc > self.CCPM_MAX_LAYERS or not all(1 <= c <= self.CCPM_MAX_FILTERS for c in self.ccpm_filters)
+                    or not 2 <= F <= self.CCPM_MAX_FIELDS or self.E not in self.CCPM_EMB
+                    or (F >> Lc) < 1 or (self.E >> Lc) < 1):
+                raise ValueError("ccpm_filters: 1 to %d layers of 1 to %d filters on 2 to %d embedded fields of "
+                                 "size %s, every layer halving the map to at least 1 x 1; got %r on %d fields "
+                                 "of size %d"
+                                 % (self.CCPM_MAX_LAYERS, self.CCPM_MAX_FILTERS, self.CCPM_MAX_FIELDS,
+                                    " / ".join(map(str, self.CCPM_EMB)), self.ccpm_filters, F, self.E))
+
     @property
     def afm_fields(self):
-        """The fields the attentional interactions pair (and the product layer mixes, and the
-        Bi-Interaction pools): single-valued, then pooled slots."""
+        """The fields the attentional interactions pair (and the product layer mixes, the
+        Bi-Interaction pools and the CCPM branch convolves): single-valued, then pooled slots."""
         return self.S + self.M
+
+    def ccpm_dims(self):
+        """[(H, W, C)] of the CCPM branch's input map and of every pooled map."""
+        out = [(self.E, self.afm_fields, 1)]
+        for c in self.ccpm_filters:
+            out.append((out[-1][0] // 2, out[-1][1] // 2, c))
+        return out
 
     @property
     def ftrl_lr(self):
@@ -414,6 +455,38 @@ class ModelSpec:
         bi = np.arange(E if self.bi_interaction else 0) + C + V + (S + M) * E
         return np.concatenate([cat, pool, bi, cont, vec])
 
+
+
+def ccpm_shapes(dims):
+    """ModelSpec.ccpm_dims() -> {variable: Keras shape} in the device vector's order: ccpm_out.kernel
+    [H_L W_L C_L, 1], then per layer ccpm_conv_{l}.kernel [3, 3, C_{l-1}, C_l] and ccpm_conv_{l}.bias [C_l]."""
+    out = {"ccpm_out.kernel": (dims[-1][0] * dims[-1][1] * dims[-1][2], 1)}
+    for l in range(len(dims) - 1):
+        out["ccpm_conv_%d.kernel" % l] = (3, 3, dims[l][2], dims[l + 1][2])
+        out["ccpm_conv_%d.bias" % l] = (dims[l + 1][2],)
+    return out
+
+
+def ccpm_pack(P, shapes):
+    """Reference-layout CCPM parameters -> the device vector [p | K_0 | b_0 | ..]; a variable of another
+    size is refused."""
+    parts = []
+    for k, shp in shapes.items():
+        a = np.asarray(P[k], np.float32)
+        if a.size != int(np.prod(shp)):
+            raise ValueError("ccpm_filters: %s holds %d values, not %s" % (k, a.size, " x ".join(map(str, shp))))
+        parts.append(a.reshape(-1))
+    return np.concatenate(parts)
+
+
+def ccpm_unpack(v, shapes):
+    """Inverse of ccpm_pack: {key: numpy in the reference's shape}."""
+    out, o = {}, 0
+    for k, shp in shapes.items():
+        n = int(np.prod(shp))
+        out[k] = np.asarray(v[o:o + n], np.float32).reshape(shp).copy()
+        o += n
+    return out
 
 
 def _root_to_v(s):
@@ -692,6 +765,21 @@ class CTREngine:
             self.afm_stats, self.z_afm = z(B, 2), z(B)
             self.afm_blocks = call_int("dl_afm_grid", B)
             self.afm_slab = z(self.afm_blocks, self.afm_n)
+        # CCPM branch (ModelSpec.ccpm_filters, csrc/ccpm.hip): the parameters as one vector
+        # [p | K_0 | b_0 | K_1 | b_1 ..] with its Adam moments, the logit z_ccpm [B] (z_afm or z_cross
+        # already added when those branches are on: the head's one z_extra) and the backward's per-block
+        # partial sums
+        self.ccpm = sp.ccpm_filters
+        if self.ccpm:
+            if type(self) is not CTREngine:
+                raise ValueError("ccpm_filters: not supported by %s" % type(self).__name__)
+            self.ccpm_n = sum(int(np.prod(shp)) for shp in self._ccpm_shapes().values())
+            self.ccpm_f = (_lib.C.c_int32 * 3)(*self.ccpm)
+            self.kw = z(_ru(self.ccpm_n, 4))
+            self.km, self.kv = torch.zeros_like(self.kw), torch.zeros_like(self.kw)
+            self.z_ccpm = z(B)
+            self.ccpm_blocks = call_int("dl_ccpm_grid", B)
+            self.ccpm_slab = z(self.ccpm_blocks, self.ccpm_n)
         # product layer (ModelSpec.pnn, csrc/pnn.hip): theta [D1, F] with its Adam moments and the
         # backward's per-block partial sums; lp itself is added into h[0] and kept nowhere
         self.pnn = sp.pnn
@@ -895,6 +983,17 @@ class CTREngine:
             P = {"attention_w": rng.standard_normal((sp.E, A)) * g, "attention_b": rng.standard_normal((1, A)) * g,
                  "attention_h": rng.standard_normal((1, A)), "attention_p": rng.standard_normal((sp.E, 1))}
             self.aw[: self.afm_n].copy_(torch.from_numpy(self._afm_pack(P)))
+        if self.ccpm:
+            # Keras' defaults (CCPM.py:56-68 passes no initializer): glorot_uniform kernels, zero biases
+            P = {}
+            for k, shp in self._ccpm_shapes().items():
+                if k.endswith(".bias"):
+                    P[k] = np.zeros(shp, np.float32)
+                else:
+                    rf = shp[0] * shp[1] if len(shp) == 4 else 1
+                    lim = math.sqrt(6.0 / (rf * (shp[-2] + shp[-1])))
+                    P[k] = rng.uniform(-lim, lim, shp)
+            self.kw[: self.ccpm_n].copy_(torch.from_numpy(self._ccpm_pack(P)))
         if self.pnn:
             # PNN.py:57: product-quadratic-inner ~ N(0, 0.01)
             v = rng.standard_normal((sp.hidden[0], sp.afm_fields)) * 0.01
@@ -975,6 +1074,8 @@ class CTREngine:
             self.aw[: self.afm_n].copy_(torch.from_numpy(self._afm_pack(P)))
         if self.pnn:
             self.pw[: self.pnn_n].copy_(torch.from_numpy(self._pnn_pack(P)))
+        if self.ccpm:
+            self.kw[: self.ccpm_n].copy_(torch.from_numpy(self._ccpm_pack(P)))
         torch.cuda.synchronize()
 
     BN_KEY = "batch_norm_%d.%s"   # NFM.py:166: setattr(self, 'batch_norm_' + str(i), ...), i from 1
@@ -1020,6 +1121,18 @@ class CTREngine:
         """Inverse of _pnn_pack on a device vector."""
         D1, F = self.spec.hidden[0], self.spec.afm_fields
         return {self.PNN_KEY: vec[: self.pnn_n].cpu().numpy().reshape(D1, F).copy()}
+
+    def _ccpm_shapes(self):
+        """The CCPM variables in the device vector's order [p | K_0 | b_0 | K_1 | b_1 ..], Keras shapes."""
+        return ccpm_shapes(self.spec.ccpm_dims())
+
+    def _ccpm_pack(self, P):
+        """Reference-layout CCPM parameters -> the device vector."""
+        return ccpm_pack(P, self._ccpm_shapes())
+
+    def _ccpm_unpack(self, vec):
+        """Inverse of _ccpm_pack on a device vector: {key: numpy in the reference's shape}."""
+        return ccpm_unpack(vec[: self.ccpm_n].cpu().numpy(), self._ccpm_shapes())
 
     AFM_KEYS = ("attention_p", "attention_h", "attention_b", "attention_w")   # the device vector's order
 
@@ -1105,7 +1218,7 @@ class CTREngine:
         layout (numpy); the wide records are caught up first."""
         ww, wz, wn = self._wide_state()
         P = self._export_dense(self.W, self.w_head, ww, getattr(self, "wb", None), getattr(self, "cw", None),
-                               getattr(self, "aw", None), getattr(self, "pw", None))
+                               getattr(self, "aw", None), getattr(self, "pw", None), getattr(self, "kw", None))
         if self.ftrl:
             P.update(self._ftrl_export(wz, wn))
         if self.bn:
@@ -1123,9 +1236,11 @@ class CTREngine:
             d.update(self._ftrl_export(wm, wv))
         else:
             d = {"m": self._export_dense(self.Wm, self.hm, wm, getattr(self, "wbm", None), getattr(self, "cm", None),
-                                         getattr(self, "am", None), getattr(self, "pm", None)),
+                                         getattr(self, "am", None), getattr(self, "pm", None),
+                                         getattr(self, "km", None)),
                  "v": self._export_dense(self.Wv, self.hv, wv, getattr(self, "wbv", None), getattr(self, "cv", None),
-                                         getattr(self, "av", None), getattr(self, "pv", None))}
+                                         getattr(self, "av", None), getattr(self, "pv", None),
+                                         getattr(self, "kv", None))}
         if self.bn:   # gamma's and beta's moments (the running statistics are state, not trained)
             d["m"].update(self._bn_unpack(self.bn_m))
             d["v"].update(self._bn_unpack(self.bn_v))
@@ -1208,7 +1323,7 @@ class CTREngine:
              ptr(self.opt), ptr(self.wsq), ptr(self.wacc), _lib.stream_handle())
         self._wsq_step = self.steps
 
-    def _export_dense(self, Ws, head, ww, wb, cross=None, afm=None, pnn=None):
+    def _export_dense(self, Ws, head, ww, wb, cross=None, afm=None, pnn=None, ccpm=None):
         """Augmented hidden-layer matrices (bias row, x0 column order), the permuted head
         vector, the wdl weights and the cross, attention and product vectors -> reference keys and
         layouts."""
@@ -1218,6 +1333,8 @@ class CTREngine:
             P.update(self._afm_unpack(afm))
         if pnn is not None:
             P.update(self._pnn_unpack(pnn))
+        if ccpm is not None:
+            P.update(self._ccpm_unpack(ccpm))
         dims = [self.D0] + sp.hidden
         for l in range(len(sp.hidden)):
             Wi = Ws[l].cpu().numpy()
@@ -1362,7 +1479,7 @@ class CTREngine:
         sp = self.spec
         if os.environ.get("DLAMD_FUSED_GATHER", "1") == "0" or not self.s3 or self.bf or sp.M:
             return False
-        if self.cross or self.afm or self.pnn or self.bi:   # all read x0's deep columns, which the fused forms leave unwritten
+        if self.cross or self.afm or self.pnn or self.bi or self.ccpm:   # all read x0's deep columns, which the fused forms leave unwritten
             return False
         if self.bn:   # the fused forms apply the ReLU themselves; layer 0 must store its pre-activation
             return False
@@ -1732,9 +1849,10 @@ class CTREngine:
                     self.head_blocks, sp.F, self._keep_thr(k1), self._keep_inv(k1), self._keep_thr(k2),
                     self._keep_inv(k2), self.seed & 0xFFFFFFFFFFFFFFFF, ptr(self.opt), ptr(self.fm_keep), s)
             return
-        if self.cross or self.afm:
+        if self.cross or self.afm or self.ccpm:
             # x0 is complete here (in lazy training the first layer's fused row gather wrote its
-            # deep columns): s and z_cross, z_afm (+ z_cross), then the head with that extra logit
+            # deep columns): s and z_cross, z_afm (+ z_cross), z_ccpm (+ those), then the head with that
+            # extra logit
             if self.cross:
                 self._c("cross_fwd", "dl_cross_fwd", B, self.D0, self.cross, ptr(self.x0), self.in_ld[0],
                         ptr(self.cw), ptr(self.cross_s), ptr(self.z_cross), s)
@@ -1742,9 +1860,14 @@ class CTREngine:
                 self._c("afm_fwd", "dl_afm_fwd", B, sp.afm_fields, sp.E, self.afm, ptr(self.x0), self.in_ld[0],
                         self.cat_col, ptr(self.aw), ptr(self.z_cross) if self.cross else None, ptr(self.afm_stats),
                         ptr(self.z_afm), s)
+            z_extra = self.z_afm if self.afm else self.z_cross if self.cross else None
+            if self.ccpm:
+                self._c("ccpm_fwd", "dl_ccpm_fwd", B, sp.afm_fields, sp.E, len(self.ccpm), self.ccpm_f, ptr(self.x0),
+                        self.in_ld[0], self.cat_col, ptr(self.kw), ptr(z_extra), ptr(self.z_ccpm), s)
+                z_extra = self.z_ccpm
             self._c("head", "dl_head_fwd_bwd_cross" + sw, B, sp.fm_cols, H, ptr(self.fm_out), self.fm_ld,
                     ptr(self.h[-1]), self.h_ld[-1], ptr(self.w_head), ptr(self.in_label), sp.logloss_eps, *scale,
-                    ptr(self.z_afm if self.afm else self.z_cross), ptr(self.score), ptr(self.z), ptr(self.dz),
+                    ptr(z_extra), ptr(self.score), ptr(self.z), ptr(self.dz),
                     ptr(self.dh[-1]), ptr(self.head_slab), self.head_blocks, s)
             return
         self._c("head", "dl_head_fwd_bwd" + sw, B, sp.fm_cols, H, ptr(self.fm_out), self.fm_ld, ptr(self.h[-1]),
@@ -1848,6 +1971,11 @@ class CTREngine:
             self._c("afm_bwd", "dl_afm_bwd", B, sp.afm_fields, sp.E, self.afm, ptr(self.x0), self.in_ld[0],
                     self.cat_col, ptr(self.aw), ptr(self.afm_stats), ptr(self.dz), ptr(self.dx0), self.dx_ld, 0,
                     ptr(self.afm_slab), self.afm_blocks, s)
+        if self.ccpm:
+            # the CCPM branch's share of dx0's field columns, likewise
+            self._c("ccpm_bwd", "dl_ccpm_bwd", B, sp.afm_fields, sp.E, len(self.ccpm), self.ccpm_f, ptr(self.x0),
+                    self.in_ld[0], self.cat_col, ptr(self.kw), ptr(self.dz), ptr(self.dx0), self.dx_ld, 0,
+                    ptr(self.ccpm_slab), self.ccpm_blocks, s)
         if self.pnn:
             # the product layer's share, from the ReluGrad-masked dh[0] the tower's backward formed
             self._c("pnn_bwd", "dl_pnn_inner_bwd", B, sp.afm_fields, sp.E, sp.hidden[0], ptr(self.x0), self.in_ld[0],
@@ -2052,6 +2180,10 @@ class CTREngine:
             # attention Adam: no regulariser on these variables (AFM.py:137 has none on them)
             self._c("adam_afm", "dl_adam_dense", ptr(self.aw), ptr(self.am), ptr(self.av), ptr(self.afm_slab),
                     call_int("dl_afm_grid", B), self.afm_n, self.afm_n, 0.0, 0, ptr(self.opt), None, None, s)
+        if self.ccpm:
+            # the CCPM variables' Adam: no regulariser (CCPM.py:73-74: the loss is the log-loss alone)
+            self._c("adam_ccpm", "dl_adam_dense", ptr(self.kw), ptr(self.km), ptr(self.kv), ptr(self.ccpm_slab),
+                    call_int("dl_ccpm_grid", B), self.ccpm_n, self.ccpm_n, 0.0, 0, ptr(self.opt), None, None, s)
         if self.pnn:
             # theta's Adam: no regulariser (PNN.py:136-139 has none on it)
             self._c("adam_pnn", "dl_adam_dense", ptr(self.pw), ptr(self.pm), ptr(self.pv), ptr(self.pnn_slab),

@@ -29,6 +29,10 @@ bi_interaction=1 (dnn_pipeline, dnn_cate, dnn_multi, dnn_multi_cate) adds the Bi
 reference's test_model/NFM.py, the sum of all pairwise products of the embedded fields, as E more columns
 of the tower input; with batch_norm=1 the model is the reference's NFM.
 
+ccpm_filters=C0,C1,.. (the same four models) adds the convolutional field interactions of the reference's
+test_model/CCPM.py beside the tower: per value a 3x3 convolution of that many filters with ReLU and a 2x2
+max-pool over the [embedding, field] map, then one more logit.
+
 wide_optimizer=ftrl wide_lr=0.05 wide_l1=1e-3 wide_l2=0 (wdl: models/wdl.py reads them from its args)
 train the wide weights with FTRL-proximal instead of Adam; L1 leaves most wide rows at exactly zero.
 
@@ -102,6 +106,8 @@ class ModelParams:
                 setattr(self, k, check_batch_norm(k, v))
             elif k == "bi_interaction":   # the Bi-Interaction pooling into the tower input, likewise
                 self.bi_interaction = check_bi_interaction(v, self.alg_name)
+            elif k == "ccpm_filters":     # the CCPM branch beside the tower, likewise
+                self.ccpm_filters = check_ccpm_filters(v, self.alg_name)
             elif k in ("wide_optimizer", "wide_lr", "wide_l1", "wide_l2"):   # stored only when given, too
                 setattr(self, k, check_wide_option(k, v, self.alg_name))
             else:
@@ -109,6 +115,8 @@ class ModelParams:
         (self.cont_field_size, self.vector_feats_size, self.cate_field_size, self.multi_feats_size,
          self.multi_field_size, self.multi_feats_range) = my_utils.feat_size(self.feat_conf_path, self.alg_name)
         check_eval_options(getattr(self, "eval_metrics", None), getattr(self, "gauc_slot", None), self.cate_field_size)
+        if hasattr(self, "ccpm_filters"):   # the map's limits, known now that the fields are counted
+            check_ccpm_map(self.ccpm_filters, self.embedding_size, self.cate_field_size + self.multi_field_size)
 
 
 EVAL_METRICS = ("auc", "gauc", "logloss", "calibration")
@@ -180,6 +188,35 @@ def check_bi_interaction(v, alg_name):
         raise SystemExit("bi_interaction=%s: the Bi-Interaction pooling feeds the tower of %s only, not %s"
                          % (v, ", ".join(ModelSpec.CROSS_MODELS), alg_name))
     return v == "1"
+
+
+def check_ccpm_filters(v, alg_name):
+    """ccpm_filters=C0,C1,.. as a list of ints; refuses (SystemExit) anything but 1 to CCPM_MAX_LAYERS
+    integers in [1, CCPM_MAX_FILTERS], and a model other than the dnn_* ones.  (The field count and the
+    embedding size are known only once the model is built: ModelSpec refuses those.)"""
+    from .engine import ModelSpec
+    try:
+        f = [int(x) for x in v.split(",")]
+    except ValueError:
+        raise SystemExit("ccpm_filters=%s is not a comma-separated list of integers" % v)
+    if not 1 <= len(f) <= ModelSpec.CCPM_MAX_LAYERS or not all(1 <= c <= ModelSpec.CCPM_MAX_FILTERS for c in f):
+        raise SystemExit("ccpm_filters=%s must hold 1 to %d values in [1, %d]"
+                         % (v, ModelSpec.CCPM_MAX_LAYERS, ModelSpec.CCPM_MAX_FILTERS))
+    if alg_name not in ModelSpec.CROSS_MODELS:
+        raise SystemExit("ccpm_filters=%s: the convolutional interactions join the tower of %s only, not %s"
+                         % (v, ", ".join(ModelSpec.CROSS_MODELS), alg_name))
+    return f
+
+
+def check_ccpm_map(filters, E, F):
+    """Refuses (SystemExit) an [E, F] field map the CCPM branch does not take: what ModelSpec would."""
+    from .engine import ModelSpec
+    Lc = len(filters)
+    if E not in ModelSpec.CCPM_EMB or not 2 <= F <= ModelSpec.CCPM_MAX_FIELDS or (F >> Lc) < 1 or (E >> Lc) < 1:
+        raise SystemExit("ccpm_filters=%s: 2 to %d embedded fields of size %s, every layer halving the map to at "
+                         "least 1 x 1; got %d fields of size %d"
+                         % (",".join(map(str, filters)), ModelSpec.CCPM_MAX_FIELDS,
+                            " / ".join(map(str, ModelSpec.CCPM_EMB)), F, E))
 
 
 def check_batch_norm(k, v):

@@ -63,6 +63,8 @@ def _spec_from_args(model, args):
             kw[k] = getattr(args, k)
     if getattr(args, "bi_interaction", None) is not None:  # local_run's bi_interaction= (stored only when given)
         kw.update(bi_interaction=bool(args.bi_interaction))
+    if getattr(args, "ccpm_filters", None) is not None:    # local_run's ccpm_filters= (stored only when given)
+        kw.update(ccpm_filters=tuple(int(c) for c in args.ccpm_filters))
     return ModelSpec(model, **kw)
 
 
@@ -242,6 +244,8 @@ def _adam_state(eng):
         out["adam/cm"], out["adam/cv"] = eng.cm.cpu().numpy(), eng.cv.cpu().numpy()
     if eng.afm:     # the attention vector's moments, in the device layout (engine.py _afm_pack)
         out["adam/am"], out["adam/av"] = eng.am.cpu().numpy(), eng.av.cpu().numpy()
+    if eng.ccpm:    # the CCPM vector's moments, in the device layout (engine.py ccpm_pack)
+        out["adam/km"], out["adam/kv"] = eng.km.cpu().numpy(), eng.kv.cpu().numpy()
     if eng.pnn:     # theta's moments, row-major [D1, F] as the device vector (engine.py _pnn_pack)
         out["adam/pm"], out["adam/pv"] = eng.pm.cpu().numpy(), eng.pv.cpu().numpy()
     if eng.bn:      # gamma's and beta's moments per hidden layer, [gamma | beta] as the device vector
@@ -270,6 +274,9 @@ def _load_adam_state(eng, d):
     if eng.afm:
         eng.am.copy_(torch.from_numpy(d["adam/am"]))
         eng.av.copy_(torch.from_numpy(d["adam/av"]))
+    if eng.ccpm:
+        eng.km.copy_(torch.from_numpy(d["adam/km"]))
+        eng.kv.copy_(torch.from_numpy(d["adam/kv"]))
     if eng.pnn:
         eng.pm.copy_(torch.from_numpy(d["adam/pm"]))
         eng.pv.copy_(torch.from_numpy(d["adam/pv"]))

@@ -188,6 +188,9 @@ class ShardedCTREngine(CTREngine):
         if spec.pnn:
             raise ValueError("pnn: not supported by ShardedCTREngine (theta's gradient is not part of the flat "
                              "all-reduce)")
+        if spec.ccpm_filters:
+            raise ValueError("ccpm_filters: not supported by ShardedCTREngine (the convolution parameters' "
+                             "gradients are not part of the flat all-reduce)")
         if spec.bi_interaction:
             raise ValueError("bi_interaction: not supported by ShardedCTREngine (its step does not launch the "
                              "pooling's kernels around the first tower layer)")

@@ -611,6 +611,32 @@ int dl_bi_bwd(int32_t B, int32_t F, int32_t E, const float* x0, int32_t ld, int3
  * blocks * 256 floats (n_out is checked). */
 int dl_vfma_probe(float* out, int64_t n_out, int32_t blocks, int32_t iters, void* stream);
 
+/* ------------------------------------------------------------------------
+ * CCPM: convolutional field interactions beside the dnn_* tower: the Conv2D(3x3, same, relu) +
+ * MaxPool2D(2x2) stack, Flatten and Dense(1) (without its bias) of test_model/CCPM.py:45-68 on the F
+ * embedded fields of x0 [B, ld], field w in columns [x_col0 + w E, x_col0 + (w + 1) E).  With
+ * X[h, w] = e_w[h], H = E, W = F, one input channel, for the L layers of filters[l] = C_l channels:
+ *   u_l[h, w, c] = b_l[c] + sum_{dh, dw in -1..1} sum_c' K_l[dh+1, dw+1, c', c] a_{l-1}[h+dh, w+dw, c']
+ *   a_l[i, j, c] = max over the 2x2 window of relu(u_l), H_l = H_{l-1} / 2, W_l = W_{l-1} / 2 (floor)
+ *   z_ccpm = sum a_{L-1}[i, j, c] p[(i W_L + j) C_L + c]
+ * params: [p (H_L W_L C_L) | K_0 (9 C_0, [3][3][1][C_0]) | b_0 | K_1 ([3][3][C_0][C_1]) | b_1 | ...].
+ * 1 <= L <= 3, 1 <= C_l <= 8, 2 <= F <= 64, E one of 8, 16, 32, F >> L >= 1; anything else is refused
+ * and nothing is written.  filters is a host array of L values.
+ * dl_ccpm_fwd writes z_out[b] = z_ccpm[b] + (z_add ? z_add[b] : 0) (z_add: the logit of the cross
+ * network and the attentional interactions, so the head's one z_extra carries all three).
+ * dl_ccpm_bwd recomputes the forward from x0 (ReLU's derivative 0 at u <= 0, the pool's gradient to the
+ * window's first maximum in (row, column) order), adds dX INTO dx0 [B, dx_ld] columns
+ * [dx_col0, dx_col0 + F E) and leaves the batch sums of the parameter gradients as per-block partials
+ * slab[block][n] in the layout of params (dl_ccpm_grid(B) blocks, at most 512; dl_adam_dense sums them
+ * in slab order).  Every per-sample map lives in LDS; no atomics: the same inputs give the same bits
+ * on every run. */
+int dl_ccpm_grid(int32_t B);
+int dl_ccpm_fwd(int32_t B, int32_t F, int32_t E, int32_t L, const int32_t* filters, const float* x0, int32_t ld,
+                int32_t x_col0, const float* params, const float* z_add, float* z_out, void* stream);
+int dl_ccpm_bwd(int32_t B, int32_t F, int32_t E, int32_t L, const int32_t* filters, const float* x0, int32_t ld,
+                int32_t x_col0, const float* params, const float* dz, float* dx0, int32_t dx_ld, int32_t dx_col0,
+                float* slab, int32_t slab_rows, void* stream);
+
 /* Wide&Deep cross logit, forward and backward fused (models/wdl.py:225-275):
  * z = sum_f w[wide_f] + sum_j w[Fw+j] h_j + bias[0] (w = wdl_weights [w_rows]; the
  * deep-output rows Fw..Fw+H alias wide ids); sigmoid + eps-log-loss as dl_head_fwd_bwd.

@@ -24,18 +24,17 @@ import gc
 import math
 import os
 import time
+from functools import partial
 
 import numpy as np
 import torch
 
 from . import _lib
 from ._lib import call, ptr
+from .param_groups import (BN_KEY, PNN_KEY, ParamGroup, _ru, afm_pack, afm_unpack, bn_pack, bn_unpack, bn_vec,
+                           ccpm_pack, ccpm_shapes, ccpm_unpack, cross_pack, cross_unpack, pnn_pack, pnn_unpack)
 
 F32 = torch.float32
-
-
-def _ru(x, m):
-    return (x + m - 1) // m * m
 
 
 # Model families of the reference's pipeline-style model files:
@@ -211,28 +210,14 @@ class ModelSpec:
             dropout_keep_fm = keep if fam["fm"] and any(k < 1.0 for k in keep) else None
         self.dropout_keep_fm = dropout_keep_fm
         if self.cross_layers:
-            if model not in self.CROSS_MODELS:
-                raise ValueError("cross_layers: the cross network joins the tower of %s only, not %s"
-                                 % (", ".join(self.CROSS_MODELS), model))
-            if tower == "bf16":
-                raise ValueError("cross_layers: not supported with tower='bf16' (the cross network reads the f32 "
-                                 "tower input)")
-            if self.dropout and self.dropout[0] < 1.0:
-                raise ValueError("cross_layers: not supported with tower-input dropout (dropout_keep_deep[0] < 1 "
-                                 "rewrites x0 in place; the cross network reads the undropped input)")
+            self._check_side_option("cross_layers", "the cross network joins", "the cross network reads the f32 "
+                                    "tower input", "the cross network reads the undropped input")
             if self.cross_layers > self.CROSS_MAX_LAYERS or self.deep_in > self.CROSS_MAX_IN:
                 raise ValueError("cross_layers: at most %d layers on at most %d tower-input columns, got %d on %d"
                                  % (self.CROSS_MAX_LAYERS, self.CROSS_MAX_IN, self.cross_layers, self.deep_in))
         if self.afm_attention:
-            if model not in self.CROSS_MODELS:
-                raise ValueError("afm_attention: the attentional interactions join the tower of %s only, not %s"
-                                 % (", ".join(self.CROSS_MODELS), model))
-            if tower == "bf16":
-                raise ValueError("afm_attention: not supported with tower='bf16' (the branch reads the f32 "
-                                 "tower input)")
-            if self.dropout and self.dropout[0] < 1.0:
-                raise ValueError("afm_attention: not supported with tower-input dropout (dropout_keep_deep[0] < 1 "
-                                 "rewrites x0 in place; the branch reads the undropped fields)")
+            self._check_side_option("afm_attention", "the attentional interactions join", "the branch reads the "
+                                    "f32 tower input", "the branch reads the undropped fields")
             if (self.afm_attention > self.AFM_MAX_ATT or not 2 <= self.afm_fields <= self.AFM_MAX_FIELDS
                     or self.E not in self.AFM_EMB):
                 raise ValueError("afm_attention: at most %d attention units on 2 to %d embedded fields of size %s, "
@@ -240,15 +225,9 @@ class ModelSpec:
                                  % (self.AFM_MAX_ATT, self.AFM_MAX_FIELDS, " / ".join(map(str, self.AFM_EMB)),
                                     self.afm_attention, self.afm_fields, self.E))
         if self.pnn:
-            if model not in self.CROSS_MODELS:
-                raise ValueError("pnn: the product layer feeds the tower of %s only, not %s"
-                                 % (", ".join(self.CROSS_MODELS), model))
-            if tower == "bf16":
-                raise ValueError("pnn: not supported with tower='bf16' (the product layer reads the f32 tower "
-                                 "input and finishes the f32 first layer)")
-            if self.dropout and self.dropout[0] < 1.0:
-                raise ValueError("pnn: not supported with tower-input dropout (dropout_keep_deep[0] < 1 rewrites "
-                                 "x0 in place; the product layer reads the undropped fields)")
+            self._check_side_option("pnn", "the product layer feeds", "the product layer reads the f32 tower "
+                                    "input and finishes the f32 first layer", "the product layer reads the "
+                                    "undropped fields")
             if self.dropout and self.dropout[1] < 1.0:
                 raise ValueError("pnn: not supported with dropout on the first layer's output "
                                  "(dropout_keep_deep[1] < 1: that layer's ReLU and dropout live in the GEMM "
@@ -271,15 +250,9 @@ class ModelSpec:
                                  "pre-activation in place)")
 
         if self.bi_interaction:
-            if model not in self.CROSS_MODELS:
-                raise ValueError("bi_interaction: the Bi-Interaction pooling feeds the tower of %s only, not %s"
-                                 % (", ".join(self.CROSS_MODELS), model))
-            if tower == "bf16":
-                raise ValueError("bi_interaction: not supported with tower='bf16' (the pooling reads and extends "
-                                 "the f32 tower input)")
-            if self.dropout and self.dropout[0] < 1.0:
-                raise ValueError("bi_interaction: not supported with tower-input dropout (dropout_keep_deep[0] < 1 "
-                                 "rewrites x0 in place; the pooling's backward reads the undropped fields)")
+            self._check_side_option("bi_interaction", "the Bi-Interaction pooling feeds", "the pooling reads and "
+                                    "extends the f32 tower input", "the pooling's backward reads the undropped "
+                                    "fields")
             if (not 2 <= self.afm_fields <= self.BI_MAX_FIELDS or self.E % 4
                     or not 4 <= self.E <= self.BI_MAX_EMB):
                 raise ValueError("bi_interaction: 2 to %d embedded fields of a size that is a multiple of 4 in "
@@ -287,15 +260,8 @@ class ModelSpec:
                                  % (self.BI_MAX_FIELDS, self.BI_MAX_EMB, self.afm_fields, self.E))
 
         if self.ccpm_filters:
-            if model not in self.CROSS_MODELS:
-                raise ValueError("ccpm_filters: the convolutional interactions join the tower of %s only, not %s"
-                                 % (", ".join(self.CROSS_MODELS), model))
-            if tower == "bf16":
-                raise ValueError("ccpm_filters: not supported with tower='bf16' (the branch reads the f32 "
-                                 "tower input)")
-            if self.dropout and self.dropout[0] < 1.0:
-                raise ValueError("ccpm_filters: not supported with tower-input dropout (dropout_keep_deep[0] < 1 "
-                                 "rewrites x0 in place; the branch reads the undropped fields)")
+            self._check_side_option("ccpm_filters", "the convolutional interactions join", "the branch reads the "
+                                    "f32 tower input", "the branch reads the undropped fields")
             Lc, F = len(self.ccpm_filters), self.afm_fields
             if (Lc > self.CCPM_MAX_LAYERS or not all(1 <= c <= self.CCPM_MAX_FILTERS for c in self.ccpm_filters)
                     or not 2 <= F <= self.CCPM_MAX_FIELDS or self.E not in self.CCPM_EMB
@@ -305,6 +271,17 @@ class ModelSpec:
                                  "of size %d"
                                  % (self.CCPM_MAX_LAYERS, self.CCPM_MAX_FILTERS, self.CCPM_MAX_FIELDS,
                                     " / ".join(map(str, self.CCPM_EMB)), self.ccpm_filters, F, self.E))
+
+    def _check_side_option(self, opt, joins, reads_f32, reads_undropped):
+        """The refusals every option on the tower input of the CROSS_MODELS shares, in that option's words."""
+        if self.model not in self.CROSS_MODELS:
+            raise ValueError("%s: %s the tower of %s only, not %s"
+                             % (opt, joins, ", ".join(self.CROSS_MODELS), self.model))
+        if self.tower == "bf16":
+            raise ValueError("%s: not supported with tower='bf16' (%s)" % (opt, reads_f32))
+        if self.dropout and self.dropout[0] < 1.0:
+            raise ValueError("%s: not supported with tower-input dropout (dropout_keep_deep[0] < 1 rewrites x0 in "
+                             "place; %s)" % (opt, reads_undropped))
 
     @property
     def afm_fields(self):
@@ -456,39 +433,6 @@ class ModelSpec:
         return np.concatenate([cat, pool, bi, cont, vec])
 
 
-
-def ccpm_shapes(dims):
-    """ModelSpec.ccpm_dims() -> {variable: Keras shape} in the device vector's order: ccpm_out.kernel
-    [H_L W_L C_L, 1], then per layer ccpm_conv_{l}.kernel [3, 3, C_{l-1}, C_l] and ccpm_conv_{l}.bias [C_l]."""
-    out = {"ccpm_out.kernel": (dims[-1][0] * dims[-1][1] * dims[-1][2], 1)}
-    for l in range(len(dims) - 1):
-        out["ccpm_conv_%d.kernel" % l] = (3, 3, dims[l][2], dims[l + 1][2])
-        out["ccpm_conv_%d.bias" % l] = (dims[l + 1][2],)
-    return out
-
-
-def ccpm_pack(P, shapes):
-    """Reference-layout CCPM parameters -> the device vector [p | K_0 | b_0 | ..]; a variable of another
-    size is refused."""
-    parts = []
-    for k, shp in shapes.items():
-        a = np.asarray(P[k], np.float32)
-        if a.size != int(np.prod(shp)):
-            raise ValueError("ccpm_filters: %s holds %d values, not %s" % (k, a.size, " x ".join(map(str, shp))))
-        parts.append(a.reshape(-1))
-    return np.concatenate(parts)
-
-
-def ccpm_unpack(v, shapes):
-    """Inverse of ccpm_pack: {key: numpy in the reference's shape}."""
-    out, o = {}, 0
-    for k, shp in shapes.items():
-        n = int(np.prod(shp))
-        out[k] = np.asarray(v[o:o + n], np.float32).reshape(shp).copy()
-        o += n
-    return out
-
-
 def _root_to_v(s):
     """Device root state s = sqrt(v) (a tensor) -> TF's v, fl(s * s), as host numpy."""
     a = s.cpu().numpy().astype(np.float64)
@@ -539,6 +483,14 @@ class CTREngine:
         if self.fmdrop and type(self) is not CTREngine:
             raise ValueError("dropout_keep_fm: not supported by %s (the mask is indexed by the local "
                              "row number; a sharded batch needs global rows)" % type(self).__name__)
+        # the options only this class's own step carries
+        for opt, on, why in (("bi_interaction", sp.bi_interaction, ""), ("cross_layers", sp.cross_layers, ""),
+                             ("afm_attention", sp.afm_attention, ""), ("ccpm_filters", sp.ccpm_filters, ""),
+                             ("pnn", sp.pnn, ""),
+                             ("batch_norm", sp.batch_norm, " (the batch statistics would need a reduction across "
+                                                           "the ranks)")):
+            if on and type(self) is not CTREngine:
+                raise ValueError("%s: not supported by %s%s" % (opt, type(self).__name__, why))
         self.dev = torch.device(device)
         self.B = max_batch
         # set later: predict's planes (flush(planes=True)) and the step they were written at,
@@ -560,8 +512,6 @@ class CTREngine:
         # last field, before cont and vector, so [fields | q] is one range of x0 and of dx0 (layer 0's
         # dX GEMM covers dq by the wider dx_cols); nothing else is allocated
         self.bi = sp.bi_interaction
-        if self.bi and type(self) is not CTREngine:
-            raise ValueError("bi_interaction: not supported by %s" % type(self).__name__)
         self.bi_col = (S + M) * E
         self.cont_col = (S + M) * E + (E if self.bi else 0)
         self.vec_col = self.cont_col + sp.C
@@ -738,81 +688,65 @@ class CTREngine:
             self.fm_drop_desc = _lib.FmDrop(fm_keep=self.fm_keep.data_ptr(), inv1=self._keep_inv(self.fmdrop[0]),
                                             inv2=self._keep_inv(self.fmdrop[1]))
         self.score, self.z, self.dz = z(B), z(B), z(B)
-        # cross network (ModelSpec.cross_layers, csrc/cross.hip): the parameters as one vector
-        # [c | w_0 .. | b_0 ..] in x0's column order with its Adam moments, the forward's s [B, L]
-        # and z_cross [B], and the backward's per-block partial sums (dl_adam_dense's slab)
-        self.cross = sp.cross_layers
+        # the branches' dense parameter vectors, each with its Adam moments and the backward's per-block
+        # partial sums (param_groups.py), in the order of their Adam launches; the enabled ones only
+        self.groups = {}
+
+        def group(name, n, pack, unpack, ckpt_keys, **kw):
+            self.groups[name] = ParamGroup(name, n, "dl_%s_grid" % name, B, dev, pack, unpack, ckpt_keys, **kw)
+        # cross network (ModelSpec.cross_layers, csrc/cross.hip): [c | w_0 .. | b_0 ..] in x0's column
+        # order, the forward's s [B, L] and z_cross [B].  L2 on c, the output layer's cross part (DCN.py:104:
+        # the whole projection), its sum of squares joining the head's in the step's regulariser sum
+        self.cross = Lc = sp.cross_layers
         if self.cross:
-            if type(self) is not CTREngine:
-                raise ValueError("cross_layers: not supported by %s" % type(self).__name__)
-            self.cross_n = (2 * self.cross + 1) * self.D0
-            self.cw = z(_ru(self.cross_n, 4))
-            self.cm, self.cv = torch.zeros_like(self.cw), torch.zeros_like(self.cw)
+            D0, rows = self.D0, sp.x0_ref_rows()
+            lay = dict(L=Lc, D0=D0, rows=rows)
+            group("cross", (2 * Lc + 1) * D0, partial(cross_pack, **lay), partial(cross_unpack, **lay),
+                  ("adam/cm", "adam/cv"), reg=(sp.l2, D0, self.opt[8:]))
             self.cross_s, self.z_cross = z(B, self.cross), z(B)
-            self.cross_blocks = call_int("dl_cross_grid", B)
-            self.cross_slab = z(self.cross_blocks, self.cross_n)
-        # attentional interactions (ModelSpec.afm_attention, csrc/afm.hip): the parameters as one vector
-        # [p (E) | h (A) | b (A) | W (E A)] with its Adam moments, the forward's softmax statistics
-        # [B, 2] and logit z_afm [B] (z_cross already added when both branches are on: the head's one
-        # z_extra), and the backward's per-block partial sums
-        self.afm = sp.afm_attention
+        # attentional interactions (ModelSpec.afm_attention, csrc/afm.hip): [p (E) | h (A) | b (A) | W (E A)],
+        # the forward's softmax statistics [B, 2] and logit z_afm [B] (z_cross already added when both
+        # branches are on: the head's one z_extra).  No regulariser (AFM.py:137 has none on these variables)
+        self.afm = A = sp.afm_attention
         if self.afm:
-            if type(self) is not CTREngine:
-                raise ValueError("afm_attention: not supported by %s" % type(self).__name__)
-            self.afm_n = E + 2 * self.afm + E * self.afm
-            self.aw = z(_ru(self.afm_n, 4))
-            self.am, self.av = torch.zeros_like(self.aw), torch.zeros_like(self.aw)
+            group("afm", E + 2 * A + E * A, partial(afm_pack, E=E, A=A), partial(afm_unpack, E=E, A=A),
+                  ("adam/am", "adam/av"))
             self.afm_stats, self.z_afm = z(B, 2), z(B)
-            self.afm_blocks = call_int("dl_afm_grid", B)
-            self.afm_slab = z(self.afm_blocks, self.afm_n)
-        # CCPM branch (ModelSpec.ccpm_filters, csrc/ccpm.hip): the parameters as one vector
-        # [p | K_0 | b_0 | K_1 | b_1 ..] with its Adam moments, the logit z_ccpm [B] (z_afm or z_cross
-        # already added when those branches are on: the head's one z_extra) and the backward's per-block
-        # partial sums
+        # CCPM branch (ModelSpec.ccpm_filters, csrc/ccpm.hip): [p | K_0 | b_0 | K_1 | b_1 ..] and the logit
+        # z_ccpm [B] (z_afm or z_cross already added when those branches are on: the head's one z_extra).
+        # No regulariser (CCPM.py:73-74: the loss is the log-loss alone)
         self.ccpm = sp.ccpm_filters
         if self.ccpm:
-            if type(self) is not CTREngine:
-                raise ValueError("ccpm_filters: not supported by %s" % type(self).__name__)
-            self.ccpm_n = sum(int(np.prod(shp)) for shp in self._ccpm_shapes().values())
+            shapes = ccpm_shapes(sp.ccpm_dims())
+            group("ccpm", sum(int(np.prod(shp)) for shp in shapes.values()), partial(ccpm_pack, shapes=shapes),
+                  partial(ccpm_unpack, shapes=shapes), ("adam/km", "adam/kv"))
             self.ccpm_f = (_lib.C.c_int32 * 3)(*self.ccpm)
-            self.kw = z(_ru(self.ccpm_n, 4))
-            self.km, self.kv = torch.zeros_like(self.kw), torch.zeros_like(self.kw)
             self.z_ccpm = z(B)
-            self.ccpm_blocks = call_int("dl_ccpm_grid", B)
-            self.ccpm_slab = z(self.ccpm_blocks, self.ccpm_n)
-        # product layer (ModelSpec.pnn, csrc/pnn.hip): theta [D1, F] with its Adam moments and the
-        # backward's per-block partial sums; lp itself is added into h[0] and kept nowhere
+        # product layer (ModelSpec.pnn, csrc/pnn.hip): theta [D1, F]; lp itself is added into h[0] and kept
+        # nowhere.  No regulariser (PNN.py:136-139 has none on it)
         self.pnn = sp.pnn
         if self.pnn:
-            if type(self) is not CTREngine:
-                raise ValueError("pnn: not supported by %s" % type(self).__name__)
-            self.pnn_n = sp.hidden[0] * sp.afm_fields
-            self.pw = z(_ru(self.pnn_n, 4))
-            self.pm, self.pv = torch.zeros_like(self.pw), torch.zeros_like(self.pw)
-            self.pnn_blocks = call_int("dl_pnn_grid", B)
-            self.pnn_slab = z(self.pnn_blocks, self.pnn_n)
-        # batch normalisation (ModelSpec.batch_norm, csrc/bn.hip), per hidden layer: [gamma | beta] with
-        # its Adam moments, [running_mean | running_var], the step's [mu_hi | mu_lo | invstd], xhat
-        # [B, h_ld] and the backward's per-block partial sums; the statistics' partials and the merged
-        # backward sums are consumed at once and shared by the layers
+            D1, F = sp.hidden[0], sp.afm_fields
+            group("pnn", D1 * F, partial(pnn_pack, D1=D1, F=F), partial(pnn_unpack, D1=D1, F=F),
+                  ("adam/pm", "adam/pv"))
+        # batch normalisation (ModelSpec.batch_norm, csrc/bn.hip), per hidden layer: [gamma | beta] as a
+        # group of its own (no regulariser), [running_mean | running_var], the step's [mu_hi | mu_lo |
+        # invstd] and xhat [B, h_ld]; the statistics' partials and the merged backward sums are consumed at
+        # once and shared by the layers
         self.bn = sp.batch_norm
+        self.bn_groups = []
         if self.bn:
-            if type(self) is not CTREngine:
-                raise ValueError("batch_norm: not supported by %s (the batch statistics would need a reduction "
-                                 "across the ranks)" % type(self).__name__)
-            self.bn_blocks = call_int("dl_bn_grid", B)
             dp = [_ru(h, 16) for h in sp.hidden]
-            self.bn_w = [z(_ru(2 * h, 4)) for h in sp.hidden]
-            for w, h in zip(self.bn_w, sp.hidden):
-                w[:h] = 1.0
-            self.bn_m = [torch.zeros_like(w) for w in self.bn_w]
-            self.bn_v = [torch.zeros_like(w) for w in self.bn_w]
+            for l, h in enumerate(sp.hidden):
+                g = ParamGroup("bn_l%d" % l, 2 * h, "dl_bn_grid", B, dev, partial(bn_pack, l=l, D=h),
+                               partial(bn_unpack, l=l, D=h), ("adam/bn_m%d" % l, "adam/bn_v%d" % l))
+                g.w[:h] = 1.0
+                self.bn_groups.append(g)
             self.bn_run = [z(2, h) for h in sp.hidden]
             for r in self.bn_run:
                 r[1] = 1.0
             self.bn_stat = [z(3 * d) for d in dp]
             self.hx = [z(B, self.h_ld[l]) for l in range(len(sp.hidden))]
-            self.bn_slab = [z(self.bn_blocks, 2 * h) for h in sp.hidden]
             self.bn_ws = z(max(call_int("dl_bn_ws_floats", B, h) for h in sp.hidden))
             self.bn_sums = z(2 * max(dp))
         self.head_grid ="dl_wdl_head_grid" if self.wdl else "dl_head_grid"   # slab rows per batch size
@@ -976,28 +910,29 @@ class CTREngine:
             D, Lc = self.D0, self.cross
             v = rng.standard_normal((2 * Lc + 1, D)) * math.sqrt(2.0 / (D + D))
             v[0] = rng.standard_normal(D) * math.sqrt(2.0 / (D + H + 1))
-            self.cw[: self.cross_n].copy_(torch.from_numpy(v.astype(np.float32).reshape(-1)))
+            cross = self.groups["cross"]     # (v is drawn in the device vector's own column order)
+            cross.load(cross.unpack(v.astype(np.float32).reshape(-1)))
         if self.afm:
             # AFM.py:75-85: attention_w, attention_b ~ N(0, sqrt(2 / (A + E))); attention_h, attention_p ~ N(0, 1)
             A, g = self.afm, math.sqrt(2.0 / (self.afm + sp.E))
             P = {"attention_w": rng.standard_normal((sp.E, A)) * g, "attention_b": rng.standard_normal((1, A)) * g,
                  "attention_h": rng.standard_normal((1, A)), "attention_p": rng.standard_normal((sp.E, 1))}
-            self.aw[: self.afm_n].copy_(torch.from_numpy(self._afm_pack(P)))
+            self.groups["afm"].load(P)
         if self.ccpm:
             # Keras' defaults (CCPM.py:56-68 passes no initializer): glorot_uniform kernels, zero biases
             P = {}
-            for k, shp in self._ccpm_shapes().items():
+            for k, shp in ccpm_shapes(sp.ccpm_dims()).items():
                 if k.endswith(".bias"):
                     P[k] = np.zeros(shp, np.float32)
                 else:
                     rf = shp[0] * shp[1] if len(shp) == 4 else 1
                     lim = math.sqrt(6.0 / (rf * (shp[-2] + shp[-1])))
                     P[k] = rng.uniform(-lim, lim, shp)
-            self.kw[: self.ccpm_n].copy_(torch.from_numpy(self._ccpm_pack(P)))
+            self.groups["ccpm"].load(P)
         if self.pnn:
             # PNN.py:57: product-quadratic-inner ~ N(0, 0.01)
             v = rng.standard_normal((sp.hidden[0], sp.afm_fields)) * 0.01
-            self.pw[: self.pnn_n].copy_(torch.from_numpy(self._pnn_pack({self.PNN_KEY: v})))
+            self.groups["pnn"].load({PNN_KEY: v})
         if self.wide_lazy:
             self._wide_pack()
         torch.cuda.synchronize()
@@ -1068,124 +1003,17 @@ class CTREngine:
         w = w[sp.head_ref_index()]
         self.w_head.zero_()
         self.w_head[: self.head_n].copy_(torch.from_numpy(w))
-        if self.cross:
-            self.cw[: self.cross_n].copy_(torch.from_numpy(self._cross_pack(P)))
-        if self.afm:
-            self.aw[: self.afm_n].copy_(torch.from_numpy(self._afm_pack(P)))
-        if self.pnn:
-            self.pw[: self.pnn_n].copy_(torch.from_numpy(self._pnn_pack(P)))
-        if self.ccpm:
-            self.kw[: self.ccpm_n].copy_(torch.from_numpy(self._ccpm_pack(P)))
+        for g in self.groups.values():
+            g.load(P)
         torch.cuda.synchronize()
-
-    BN_KEY = "batch_norm_%d.%s"   # NFM.py:166: setattr(self, 'batch_norm_' + str(i), ...), i from 1
 
     def _bn_load(self, P):
         """Reference-layout gamma, beta and running statistics of every hidden layer -> the device
         (absent running statistics: torch's initial 0 and 1)."""
-        for l, D in enumerate(self.spec.hidden):
-            def get(part, default=None):
-                k = self.BN_KEY % (l + 1, part)
-                if k not in P and default is not None:
-                    return np.full(D, default, np.float32)
-                a = np.ascontiguousarray(P[k], np.float32).reshape(-1)
-                if a.size != D:
-                    raise ValueError("%s holds %d values for %d units" % (k, a.size, D))
-                return a
-            self.bn_w[l][: 2 * D].copy_(torch.from_numpy(np.concatenate([get("weight"), get("bias")])))
-            self.bn_run[l].copy_(torch.from_numpy(np.stack([get("running_mean", 0.0), get("running_var", 1.0)])))
-
-    def _bn_unpack(self, vecs, run=None):
-        """Per-layer [gamma | beta] vectors (and [running_mean | running_var]) -> reference keys."""
-        out = {}
-        for l, D in enumerate(self.spec.hidden):
-            v = vecs[l][: 2 * D].cpu().numpy()
-            out[self.BN_KEY % (l + 1, "weight")], out[self.BN_KEY % (l + 1, "bias")] = v[:D].copy(), v[D:].copy()
-            if run is not None:
-                r = run[l].cpu().numpy()
-                out[self.BN_KEY % (l + 1, "running_mean")] = r[0].copy()
-                out[self.BN_KEY % (l + 1, "running_var")] = r[1].copy()
-        return out
-
-    PNN_KEY = "product-quadratic-inner"   # PNN.py:57, [D1, F]: the device vector is its row-major image
-
-    def _pnn_pack(self, P):
-        """Reference-layout theta [D1, F] -> the device vector."""
-        D1, F = self.spec.hidden[0], self.spec.afm_fields
-        a = np.asarray(P[self.PNN_KEY], np.float32)
-        if a.shape != (D1, F):
-            raise ValueError("%s has shape %r, not (%d, %d)" % (self.PNN_KEY, a.shape, D1, F))
-        return np.ascontiguousarray(a).reshape(-1)
-
-    def _pnn_unpack(self, vec):
-        """Inverse of _pnn_pack on a device vector."""
-        D1, F = self.spec.hidden[0], self.spec.afm_fields
-        return {self.PNN_KEY: vec[: self.pnn_n].cpu().numpy().reshape(D1, F).copy()}
-
-    def _ccpm_shapes(self):
-        """The CCPM variables in the device vector's order [p | K_0 | b_0 | K_1 | b_1 ..], Keras shapes."""
-        return ccpm_shapes(self.spec.ccpm_dims())
-
-    def _ccpm_pack(self, P):
-        """Reference-layout CCPM parameters -> the device vector."""
-        return ccpm_pack(P, self._ccpm_shapes())
-
-    def _ccpm_unpack(self, vec):
-        """Inverse of _ccpm_pack on a device vector: {key: numpy in the reference's shape}."""
-        return ccpm_unpack(vec[: self.ccpm_n].cpu().numpy(), self._ccpm_shapes())
-
-    AFM_KEYS = ("attention_p", "attention_h", "attention_b", "attention_w")   # the device vector's order
-
-    def _afm_shapes(self):
-        E, A = self.spec.E, self.afm
-        return {"attention_p": (E, 1), "attention_h": (1, A), "attention_b": (1, A), "attention_w": (E, A)}
-
-    def _afm_pack(self, P):
-        """Reference-layout attention parameters (AFM.py:75-85) -> the device vector [p | h | b | W]."""
-        parts = []
-        for k, shp in self._afm_shapes().items():
-            a = np.asarray(P[k], np.float32)
-            if a.size != shp[0] * shp[1]:
-                raise ValueError("%s holds %d values, not %d x %d" % (k, a.size, shp[0], shp[1]))
-            parts.append(a.reshape(-1))
-        return np.concatenate(parts)
-
-    def _afm_unpack(self, vec):
-        """Inverse of _afm_pack on a device vector: {key: numpy in the reference's shape}."""
-        v = vec[: self.afm_n].cpu().numpy()
-        out, o = {}, 0
-        for k, shp in self._afm_shapes().items():
-            out[k] = v[o:o + shp[0] * shp[1]].reshape(shp).copy()
-            o += shp[0] * shp[1]
-        return out
-
-    def _cross_keys(self):
-        """Reference keys of the cross vector's (2L + 1) parts, in its order [c | w_l | b_l]."""
-        Lc = self.cross
-        return ["cross_res"] + ["cross_layer_%d" % l for l in range(Lc)] + ["cross_bias_%d" % l for l in range(Lc)]
-
-    def _cross_pack(self, P):
-        """Reference-layout cross parameters ([D, 1] each, rows in the reference's deep-input
-        order) -> the device vector (x0's column order)."""
-        rows = self.spec.x0_ref_rows()
-        parts = []
-        for k in self._cross_keys():
-            a = np.asarray(P[k], np.float32).reshape(-1)
-            if a.size != self.D0:
-                raise ValueError("%s holds %d values for %d tower-input columns" % (k, a.size, self.D0))
-            parts.append(a[rows])
-        return np.concatenate(parts)
-
-    def _cross_unpack(self, vec):
-        """Inverse of _cross_pack on a device vector: {key: [D, 1] numpy}."""
-        rows = self.spec.x0_ref_rows()
-        v = vec[: self.cross_n].cpu().numpy().reshape(2 * self.cross + 1, self.D0)
-        out = {}
-        for i, k in enumerate(self._cross_keys()):
-            a = np.empty(self.D0, np.float32)
-            a[rows] = v[i]
-            out[k] = a[:, None]
-        return out
+        for l, (g, D) in enumerate(zip(self.bn_groups, self.spec.hidden)):
+            g.load(P)
+            self.bn_run[l].copy_(torch.from_numpy(np.stack([bn_vec(P, l, "running_mean", D, 0.0),
+                                                            bn_vec(P, l, "running_var", D, 1.0)])))
 
     def params(self):
         """Export parameters in the reference layout (numpy)."""
@@ -1213,37 +1041,33 @@ class CTREngine:
             return [_bf16_dw_splits(i, B, base) for i in self.in_ld]
         return [_s3_dw_splits(i, o, B, base) for i, o in zip(self.in_ld, self.spec.hidden)]
 
+    def all_groups(self):
+        """Every ParamGroup: the branches', then batch norm's of each hidden layer."""
+        return [*self.groups.values(), *self.bn_groups]
+
     def dense_params(self):
-        """The dense parameters (hidden layers, head or wdl weights + bias) in the reference
-        layout (numpy); the wide records are caught up first."""
+        """The dense parameters (hidden layers, head or wdl weights + bias, the branches' and batch
+        norm's vectors) in the reference layout (numpy); the wide records are caught up first."""
         ww, wz, wn = self._wide_state()
-        P = self._export_dense(self.W, self.w_head, ww, getattr(self, "wb", None), getattr(self, "cw", None),
-                               getattr(self, "aw", None), getattr(self, "pw", None), getattr(self, "kw", None))
+        P = self._export_dense(self.W, self.w_head, ww, self.wb if self.wdl else None, "w")
         if self.ftrl:
             P.update(self._ftrl_export(wz, wn))
-        if self.bn:
-            P.update(self._bn_unpack(self.bn_w, self.bn_run))
+        for l, r in enumerate(self.bn_run if self.bn else ()):
+            r = r.cpu().numpy()
+            P[BN_KEY % (l + 1, "running_mean")], P[BN_KEY % (l + 1, "running_var")] = r[0].copy(), r[1].copy()
         return P
 
     def dense_state(self):
-        """Adam moments of the dense parameters (hidden layers, head / wdl weights) in the
-        reference layout: {"m": {key: array}, "v": {key: array}} (tests; the table's are in
-        adam_state())."""
+        """Adam moments of the dense parameters (hidden layers, head / wdl weights, the branches' and
+        batch norm's vectors; the running statistics are state, not trained) in the reference layout:
+        {"m": {key: array}, "v": {key: array}} (tests; the table's are in adam_state())."""
         _, wm, wv = self._wide_state()
-        if self.ftrl:   # no Adam moments of wdl_weights: FTRL's z and n under their own names
-            d = {"m": self._export_dense(self.Wm, self.hm, None, self.wbm, None),
-                 "v": self._export_dense(self.Wv, self.hv, None, self.wbv, None)}
+        wbm, wbv = (self.wbm, self.wbv) if self.wdl else (None, None)
+        # FTRL: no Adam moments of wdl_weights, its z and n under their own names
+        d = {"m": self._export_dense(self.Wm, self.hm, None if self.ftrl else wm, wbm, "m"),
+             "v": self._export_dense(self.Wv, self.hv, None if self.ftrl else wv, wbv, "v")}
+        if self.ftrl:
             d.update(self._ftrl_export(wm, wv))
-        else:
-            d = {"m": self._export_dense(self.Wm, self.hm, wm, getattr(self, "wbm", None), getattr(self, "cm", None),
-                                         getattr(self, "am", None), getattr(self, "pm", None),
-                                         getattr(self, "km", None)),
-                 "v": self._export_dense(self.Wv, self.hv, wv, getattr(self, "wbv", None), getattr(self, "cv", None),
-                                         getattr(self, "av", None), getattr(self, "pv", None),
-                                         getattr(self, "kv", None))}
-        if self.bn:   # gamma's and beta's moments (the running statistics are state, not trained)
-            d["m"].update(self._bn_unpack(self.bn_m))
-            d["v"].update(self._bn_unpack(self.bn_v))
         return d
 
     # ------------------------------------------------------------------ wide records (wdl)
@@ -1323,18 +1147,13 @@ class CTREngine:
              ptr(self.opt), ptr(self.wsq), ptr(self.wacc), _lib.stream_handle())
         self._wsq_step = self.steps
 
-    def _export_dense(self, Ws, head, ww, wb, cross=None, afm=None, pnn=None, ccpm=None):
-        """Augmented hidden-layer matrices (bias row, x0 column order), the permuted head
-        vector, the wdl weights and the cross, attention and product vectors -> reference keys and
-        layouts."""
+    def _export_dense(self, Ws, head, ww, wb, which):
+        """Augmented hidden-layer matrices (bias row, x0 column order), the permuted head vector, the
+        wdl weights and the groups' vectors `which` (w, m or v) -> reference keys and layouts."""
         sp = self.spec
-        P = self._cross_unpack(cross) if cross is not None else {}
-        if afm is not None:
-            P.update(self._afm_unpack(afm))
-        if pnn is not None:
-            P.update(self._pnn_unpack(pnn))
-        if ccpm is not None:
-            P.update(self._ccpm_unpack(ccpm))
+        P = {}
+        for g in self.all_groups():
+            P.update(g.export(which))
         dims = [self.D0] + sp.hidden
         for l in range(len(sp.hidden)):
             Wi = Ws[l].cpu().numpy()
@@ -1601,9 +1420,7 @@ class CTREngine:
         """dl_gemm_s3_nt_drop / dl_dropout_apply's (keep_thr, inv, seed, layer, opt) of tensor
         `layer` (include/dlamd.h "Dropout": 0 = the tower input, l + 1 = hidden layer l's output)."""
         keep = self.drop[layer]
-        thr = min(int(math.floor(keep * 4294967296.0)), 4294967295)
-        inv = float(np.float32(1.0) / np.float32(keep))
-        return thr, inv, self.seed & 0xFFFFFFFFFFFFFFFF, layer, ptr(self.opt)
+        return self._keep_thr(keep), self._keep_inv(keep), self.seed & 0xFFFFFFFFFFFFFFFF, layer, ptr(self.opt)
 
     def _dropping(self, layer):
         return bool(self.drop) and self.drop[layer] < 1.0
@@ -1774,34 +1591,27 @@ class CTREngine:
                     ptr(self.bn_stat[l]), ptr(run[0]), ptr(run[1]), ptr(self.opt), ptr(self.bn_ws),
                     self.bn_ws.numel(), s)
             self._c("bn_fwd_l%d" % l, "dl_bn_fwd", B, D, ptr(self.h[l]), self.h_ld[l], ptr(self.bn_stat[l]), None,
-                    None, sp.bn_eps, ptr(self.bn_w[l]), ptr(self.hx[l]), self.h_ld[l], *bits, s)
+                    None, sp.bn_eps, ptr(self.bn_groups[l].w), ptr(self.hx[l]), self.h_ld[l], *bits, s)
         else:
             self._c("bn_fwd_l%d" % l, "dl_bn_fwd", B, D, ptr(self.h[l]), self.h_ld[l], None, ptr(run[0]),
-                    ptr(run[1]), sp.bn_eps, ptr(self.bn_w[l]), None, 0, *bits, s)
+                    ptr(run[1]), sp.bn_eps, ptr(self.bn_groups[l].w), None, 0, *bits, s)
 
     def _bn_bwd(self, l, B, s):
         """Layer l's batch-norm backward on the ReluGrad-masked dh[l]: dgamma / dbeta as slab rows for
         the layer's Adam, then dh[l] rewritten in place into the gradient of the pre-activation."""
-        D = self.spec.hidden[l]
-        nb = call_int("dl_bn_grid", B)
+        D, g = self.spec.hidden[l], self.bn_groups[l]
+        nb = g.rows(B)
         self._c("bn_sums_l%d" % l, "dl_bn_bwd_sums", B, D, ptr(self.dh[l]), self.h_ld[l], ptr(self.hx[l]),
-                self.h_ld[l], ptr(self.bn_slab[l]), nb, s)
+                self.h_ld[l], ptr(g.slab), nb, s)
         self._c("bn_apply_l%d" % l, "dl_bn_bwd_apply", B, D, ptr(self.dh[l]), self.h_ld[l], ptr(self.hx[l]),
-                self.h_ld[l], ptr(self.bn_w[l]), ptr(self.bn_stat[l]), ptr(self.bn_slab[l]), nb, ptr(self.bn_sums), s)
-
-    def _bn_adam(self, B, s):
-        """gamma / beta's Adam, a layer at a time from its slab rows: no regulariser."""
-        nb = call_int("dl_bn_grid", B)
-        for l, D in enumerate(self.spec.hidden):
-            self._c("adam_bn_l%d" % l, "dl_adam_dense", ptr(self.bn_w[l]), ptr(self.bn_m[l]), ptr(self.bn_v[l]),
-                    ptr(self.bn_slab[l]), nb, 2 * D, 2 * D, 0.0, 0, ptr(self.opt), None, None, s)
+                self.h_ld[l], ptr(g.w), ptr(self.bn_stat[l]), ptr(g.slab), nb, ptr(self.bn_sums), s)
 
     def _pnn_fwd(self, B, bits, s):
         """h[0] = relu(h[0] + lp): the product layer on layer 0's stored pre-activation (x0 is complete:
         in lazy training the first layer's fused row gather wrote its deep columns)."""
         sp = self.spec
         self._c("pnn_fwd", "dl_pnn_inner_fwd", B, sp.afm_fields, sp.E, sp.hidden[0], ptr(self.x0), self.in_ld[0],
-                self.cat_col, ptr(self.pw), ptr(self.h[0]), self.h_ld[0], *bits, s)
+                self.cat_col, ptr(self.groups["pnn"].w), ptr(self.h[0]), self.h_ld[0], *bits, s)
 
     def _head(self, B, s, train):
         """The output layer, the loss and its gradients dz and dh[-1]: the wdl cross logit (wide
@@ -1855,15 +1665,15 @@ class CTREngine:
             # extra logit
             if self.cross:
                 self._c("cross_fwd", "dl_cross_fwd", B, self.D0, self.cross, ptr(self.x0), self.in_ld[0],
-                        ptr(self.cw), ptr(self.cross_s), ptr(self.z_cross), s)
+                        ptr(self.groups["cross"].w), ptr(self.cross_s), ptr(self.z_cross), s)
             if self.afm:
                 self._c("afm_fwd", "dl_afm_fwd", B, sp.afm_fields, sp.E, self.afm, ptr(self.x0), self.in_ld[0],
-                        self.cat_col, ptr(self.aw), ptr(self.z_cross) if self.cross else None, ptr(self.afm_stats),
-                        ptr(self.z_afm), s)
+                        self.cat_col, ptr(self.groups["afm"].w), ptr(self.z_cross) if self.cross else None,
+                        ptr(self.afm_stats), ptr(self.z_afm), s)
             z_extra = self.z_afm if self.afm else self.z_cross if self.cross else None
             if self.ccpm:
                 self._c("ccpm_fwd", "dl_ccpm_fwd", B, sp.afm_fields, sp.E, len(self.ccpm), self.ccpm_f, ptr(self.x0),
-                        self.in_ld[0], self.cat_col, ptr(self.kw), ptr(z_extra), ptr(self.z_ccpm), s)
+                        self.in_ld[0], self.cat_col, ptr(self.groups["ccpm"].w), ptr(z_extra), ptr(self.z_ccpm), s)
                 z_extra = self.z_ccpm
             self._c("head", "dl_head_fwd_bwd_cross" + sw, B, sp.fm_cols, H, ptr(self.fm_out), self.fm_ld,
                     ptr(self.h[-1]), self.h_ld[-1], ptr(self.w_head), ptr(self.in_label), sp.logloss_eps, *scale,
@@ -1963,24 +1773,28 @@ class CTREngine:
         if self.cross:
             # gemm_dx_l0 has written dx0 (the embedding columns of x0, from column cat_col); the cross
             # network's share is added before the embedding backward reads it
-            self._c("cross_bwd", "dl_cross_bwd", B, self.D0, self.cross, ptr(self.x0), self.in_ld[0], ptr(self.cw),
+            g = self.groups["cross"]
+            self._c("cross_bwd", "dl_cross_bwd", B, self.D0, self.cross, ptr(self.x0), self.in_ld[0], ptr(g.w),
                     ptr(self.cross_s), ptr(self.dz), ptr(self.dx0), self.dx_ld, self.cat_col, self.dx_cols,
-                    ptr(self.cross_slab), self.cross_blocks, s)
+                    ptr(g.slab), g.blocks, s)
         if self.afm:
             # the attentional interactions' share of dx0's field columns, likewise before the embedding backward
+            g = self.groups["afm"]
             self._c("afm_bwd", "dl_afm_bwd", B, sp.afm_fields, sp.E, self.afm, ptr(self.x0), self.in_ld[0],
-                    self.cat_col, ptr(self.aw), ptr(self.afm_stats), ptr(self.dz), ptr(self.dx0), self.dx_ld, 0,
-                    ptr(self.afm_slab), self.afm_blocks, s)
+                    self.cat_col, ptr(g.w), ptr(self.afm_stats), ptr(self.dz), ptr(self.dx0), self.dx_ld, 0,
+                    ptr(g.slab), g.blocks, s)
         if self.ccpm:
             # the CCPM branch's share of dx0's field columns, likewise
+            g = self.groups["ccpm"]
             self._c("ccpm_bwd", "dl_ccpm_bwd", B, sp.afm_fields, sp.E, len(self.ccpm), self.ccpm_f, ptr(self.x0),
-                    self.in_ld[0], self.cat_col, ptr(self.kw), ptr(self.dz), ptr(self.dx0), self.dx_ld, 0,
-                    ptr(self.ccpm_slab), self.ccpm_blocks, s)
+                    self.in_ld[0], self.cat_col, ptr(g.w), ptr(self.dz), ptr(self.dx0), self.dx_ld, 0,
+                    ptr(g.slab), g.blocks, s)
         if self.pnn:
             # the product layer's share, from the ReluGrad-masked dh[0] the tower's backward formed
+            g = self.groups["pnn"]
             self._c("pnn_bwd", "dl_pnn_inner_bwd", B, sp.afm_fields, sp.E, sp.hidden[0], ptr(self.x0), self.in_ld[0],
-                    self.cat_col, ptr(self.pw), ptr(self.dh[0]), self.h_ld[0], ptr(self.dx0), self.dx_ld, 0,
-                    ptr(self.pnn_slab), self.pnn_blocks, s)
+                    self.cat_col, ptr(g.w), ptr(self.dh[0]), self.h_ld[0], ptr(self.dx0), self.dx_ld, 0,
+                    ptr(g.slab), g.blocks, s)
         if self.bi:
             # the pooling's share: dq is dx0's columns after the fields (gemm_dx_l0's wider range, plus
             # the cross network's share of them), complete here
@@ -2128,8 +1942,8 @@ class CTREngine:
                  ptr(self.touched), *fd, s)
         H = sp.hidden[-1]
         hb = call_int(self.head_grid, B)
-        if self.bn:   # (before the families part ways: wdl has gamma and beta too)
-            self._bn_adam(B, s)
+        for g in self.bn_groups:   # (before the families part ways: wdl has gamma and beta too)
+            g.adam(self, B, s)
         if self.wdl and self.wide_lazy:
             # wdl_weights, lazy: the deep-output rows' batch sums folded into the local gradient,
             # then TF1 Adam (L2 on every row, wdl.py:270-271) on the batch's unique wide rows and
@@ -2170,24 +1984,8 @@ class CTREngine:
         self._c("adam_head", "dl_adam_dense", ptr(self.w_head), ptr(self.hm), ptr(self.hv), ptr(self.head_slab),
                 hb, sp.fm_cols + H + 2, self.head_n, sp.l2 if sp.head_l2 else 0.0,
                 self.head_n - 1 if sp.head_l2 else 0, ptr(self.opt), ptr(self.w_head_prev), ptr(self.opt[8:]), s)
-        if self.cross:
-            # cross Adam: L2 on c, the output layer's cross part (DCN.py:104: the whole projection),
-            # its sum of squares joining the head's in the step's regulariser sum
-            self._c("adam_cross", "dl_adam_dense", ptr(self.cw), ptr(self.cm), ptr(self.cv), ptr(self.cross_slab),
-                    call_int("dl_cross_grid", B), self.cross_n, self.cross_n, sp.l2, self.D0, ptr(self.opt), None,
-                    ptr(self.opt[8:]), s)
-        if self.afm:
-            # attention Adam: no regulariser on these variables (AFM.py:137 has none on them)
-            self._c("adam_afm", "dl_adam_dense", ptr(self.aw), ptr(self.am), ptr(self.av), ptr(self.afm_slab),
-                    call_int("dl_afm_grid", B), self.afm_n, self.afm_n, 0.0, 0, ptr(self.opt), None, None, s)
-        if self.ccpm:
-            # the CCPM variables' Adam: no regulariser (CCPM.py:73-74: the loss is the log-loss alone)
-            self._c("adam_ccpm", "dl_adam_dense", ptr(self.kw), ptr(self.km), ptr(self.kv), ptr(self.ccpm_slab),
-                    call_int("dl_ccpm_grid", B), self.ccpm_n, self.ccpm_n, 0.0, 0, ptr(self.opt), None, None, s)
-        if self.pnn:
-            # theta's Adam: no regulariser (PNN.py:136-139 has none on it)
-            self._c("adam_pnn", "dl_adam_dense", ptr(self.pw), ptr(self.pm), ptr(self.pv), ptr(self.pnn_slab),
-                    call_int("dl_pnn_grid", B), self.pnn_n, self.pnn_n, 0.0, 0, ptr(self.opt), None, None, s)
+        for g in self.groups.values():   # the branches' vectors, each with its own regulariser arguments
+            g.adam(self, B, s)
         if self.lazy:
             return
         if sp.fm:

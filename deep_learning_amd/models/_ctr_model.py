@@ -240,17 +240,8 @@ def _adam_state(eng):
     if eng.ftrl:   # the wide bias stays with Adam: its moments, for a bit-exact continuation
         out["adam/wbm"], out["adam/wbv"] = eng.wbm.cpu().numpy(), eng.wbv.cpu().numpy()
     out["adam/hm"], out["adam/hv"] = eng.hm.cpu().numpy(), eng.hv.cpu().numpy()
-    if eng.cross:   # the cross vector's moments, in the device layout (engine.py _cross_pack)
-        out["adam/cm"], out["adam/cv"] = eng.cm.cpu().numpy(), eng.cv.cpu().numpy()
-    if eng.afm:     # the attention vector's moments, in the device layout (engine.py _afm_pack)
-        out["adam/am"], out["adam/av"] = eng.am.cpu().numpy(), eng.av.cpu().numpy()
-    if eng.ccpm:    # the CCPM vector's moments, in the device layout (engine.py ccpm_pack)
-        out["adam/km"], out["adam/kv"] = eng.km.cpu().numpy(), eng.kv.cpu().numpy()
-    if eng.pnn:     # theta's moments, row-major [D1, F] as the device vector (engine.py _pnn_pack)
-        out["adam/pm"], out["adam/pv"] = eng.pm.cpu().numpy(), eng.pv.cpu().numpy()
-    if eng.bn:      # gamma's and beta's moments per hidden layer, [gamma | beta] as the device vector
-        for l in range(len(eng.W)):
-            out["adam/bn_m%d" % l], out["adam/bn_v%d" % l] = eng.bn_m[l].cpu().numpy(), eng.bn_v[l].cpu().numpy()
+    for g in eng.all_groups():   # the branches' and batch norm's vectors' moments, in the device layout
+        out[g.ckpt_keys[0]], out[g.ckpt_keys[1]] = g.m.cpu().numpy(), g.v.cpu().numpy()
     for l in range(len(eng.W)):
         out["adam/Wm%d" % l] = eng.Wm[l].cpu().numpy()
         out["adam/Wv%d" % l] = eng.Wv[l].cpu().numpy()
@@ -268,22 +259,9 @@ def _load_adam_state(eng, d):
         eng.wbv.copy_(torch.from_numpy(d["adam/wbv"]))
     eng.hm.copy_(torch.from_numpy(d["adam/hm"]))
     eng.hv.copy_(torch.from_numpy(d["adam/hv"]))
-    if eng.cross:
-        eng.cm.copy_(torch.from_numpy(d["adam/cm"]))
-        eng.cv.copy_(torch.from_numpy(d["adam/cv"]))
-    if eng.afm:
-        eng.am.copy_(torch.from_numpy(d["adam/am"]))
-        eng.av.copy_(torch.from_numpy(d["adam/av"]))
-    if eng.ccpm:
-        eng.km.copy_(torch.from_numpy(d["adam/km"]))
-        eng.kv.copy_(torch.from_numpy(d["adam/kv"]))
-    if eng.pnn:
-        eng.pm.copy_(torch.from_numpy(d["adam/pm"]))
-        eng.pv.copy_(torch.from_numpy(d["adam/pv"]))
-    if eng.bn:
-        for l in range(len(eng.W)):
-            eng.bn_m[l].copy_(torch.from_numpy(d["adam/bn_m%d" % l]))
-            eng.bn_v[l].copy_(torch.from_numpy(d["adam/bn_v%d" % l]))
+    for g in eng.all_groups():
+        g.m.copy_(torch.from_numpy(d[g.ckpt_keys[0]]))
+        g.v.copy_(torch.from_numpy(d[g.ckpt_keys[1]]))
     for l in range(len(eng.W)):
         eng.Wm[l].copy_(torch.from_numpy(d["adam/Wm%d" % l]))
         eng.Wv[l].copy_(torch.from_numpy(d["adam/Wv%d" % l]))

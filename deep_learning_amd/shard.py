@@ -179,24 +179,17 @@ class ShardedCTREngine(CTREngine):
         if spec.dropout_keep_fm:
             raise ValueError("dropout_keep_fm: not supported by ShardedCTREngine (the mask is indexed by the "
                              "local row number; a sharded batch needs global rows)")
-        if spec.cross_layers:
-            raise ValueError("cross_layers: not supported by ShardedCTREngine (the cross parameters' gradients "
-                             "are not part of the flat all-reduce)")
-        if spec.afm_attention:
-            raise ValueError("afm_attention: not supported by ShardedCTREngine (the attention parameters' "
-                             "gradients are not part of the flat all-reduce)")
-        if spec.pnn:
-            raise ValueError("pnn: not supported by ShardedCTREngine (theta's gradient is not part of the flat "
-                             "all-reduce)")
-        if spec.ccpm_filters:
-            raise ValueError("ccpm_filters: not supported by ShardedCTREngine (the convolution parameters' "
-                             "gradients are not part of the flat all-reduce)")
-        if spec.bi_interaction:
-            raise ValueError("bi_interaction: not supported by ShardedCTREngine (its step does not launch the "
-                             "pooling's kernels around the first tower layer)")
-        if spec.batch_norm:
-            raise ValueError("batch_norm: not supported by ShardedCTREngine (the batch statistics would need a "
-                             "reduction across the ranks)")
+        flat = "gradients are not part of the flat all-reduce"
+        for opt, on, why in (
+                ("cross_layers", spec.cross_layers, "the cross parameters' " + flat),
+                ("afm_attention", spec.afm_attention, "the attention parameters' " + flat),
+                ("pnn", spec.pnn, "theta's gradient is not part of the flat all-reduce"),
+                ("ccpm_filters", spec.ccpm_filters, "the convolution parameters' " + flat),
+                ("bi_interaction", spec.bi_interaction, "its step does not launch the pooling's kernels around the "
+                                                        "first tower layer"),
+                ("batch_norm", spec.batch_norm, "the batch statistics would need a reduction across the ranks")):
+            if on:
+                raise ValueError("%s: not supported by ShardedCTREngine (%s)" % (opt, why))
         # the status ring holds 4 reports (slot k & 3) and the host reads report k only after
         # k + lag was submitted: lag <= 3, or report k + 4 overwrites k before it is read
         if not 0 <= int(lag) <= 3:

@@ -568,7 +568,7 @@ def test_default_queues_the_kernels_it_queued(hip_lib, name, adam, monkeypatch):
         torch.cuda.synchronize()
         seqs.append(list(names))
         if not extra.get("batch_norm"):
-            assert not any(hasattr(eng, a) for a in ("bn_w", "bn_run", "bn_stat", "hx", "bn_slab", "bn_ws"))
+            assert eng.bn_groups == [] and not any(hasattr(eng, a) for a in ("bn_run", "bn_stat", "hx", "bn_ws"))
     assert seqs[0] == seqs[1] and len(seqs[0]) > 8
     assert not any("dl_bn" in n for n in seqs[0])
     rest = list(seqs[2])

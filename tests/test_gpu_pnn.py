@@ -463,7 +463,7 @@ def test_default_queues_the_kernels_it_queued(hip_lib, adam, monkeypatch):
         torch.cuda.synchronize()
         seqs.append(list(names))
         if not extra.get("pnn"):
-            assert not any(hasattr(eng, a) for a in ("pw", "pm", "pv", "pnn_slab"))
+            assert "pnn" not in eng.groups
     assert seqs[0] == seqs[1] and len(seqs[0]) > 8
     assert not any("pnn" in n for n in seqs[0])
     rest = list(seqs[2])

@@ -151,9 +151,13 @@ SIGNATURES = {
     "dl_head_fwd_bwd_cross_weighted": (I32, [I32, I32, I32, P, I32, P, I32, P, P, F, P, P, P, P, P, P, P, P, I32,
                                              P]),
     "dl_vfma_probe": (I32, [P, I64, I32, I32, P]),
+    "dl_mfma_f32_probe": (I32, [P, I64, I32, I32, P]),
     "dl_ccpm_grid": (I32, [I32]),
     "dl_ccpm_fwd": (I32, [I32, I32, I32, I32, P, P, I32, I32, P, P, P, P]),
     "dl_ccpm_bwd": (I32, [I32, I32, I32, I32, P, P, I32, I32, P, P, P, I32, I32, P, I32, P]),
+    "dl_cin_grid": (I32, [I32]),
+    "dl_cin_fwd": (I32, [I32, I32, I32, I32, P, P, I32, I32, P, P, P, P]),
+    "dl_cin_bwd": (I32, [I32, I32, I32, I32, P, P, I32, I32, P, P, P, I32, I32, P, I32, P]),
     "dl_afm_grid": (I32, [I32]),
     "dl_afm_fwd": (I32, [I32, I32, I32, I32, P, I32, I32, P, P, P, P, P]),
     "dl_afm_bwd": (I32, [I32, I32, I32, I32, P, I32, I32, P, P, P, P, I32, I32, P, I32, P]),

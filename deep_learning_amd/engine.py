@@ -32,7 +32,7 @@ import torch
 from . import _lib
 from ._lib import call, ptr
 from .param_groups import (BN_KEY, PNN_KEY, ParamGroup, _ru, afm_pack, afm_unpack, bn_pack, bn_unpack, bn_vec,
-                           ccpm_pack, ccpm_shapes, ccpm_unpack, cross_pack, cross_unpack, pnn_pack, pnn_unpack)
+                           ccpm_pack, ccpm_shapes, ccpm_unpack, cin_pack, cin_shapes, cin_unpack, cross_pack, cross_unpack, pnn_pack, pnn_unpack)
 
 F32 = torch.float32
 
@@ -109,6 +109,13 @@ class ModelSpec:
     embedded fields, Flatten, Dense(1) without its bias, its logit added to the tower's (after the cross
     network's and the attentional interactions'); parameters ccpm_conv_{l}.kernel [3, 3, C_{l-1}, C_l],
     ccpm_conv_{l}.bias [C_l], ccpm_out.kernel [H_L W_L C_L, 1], no regulariser; (): none.
+    cin_layers: the feature maps (H_1, .., H_L) of a Compressed Interaction Network (xDeepFM, Lian et al. 2018,
+    eq. 6-8: direct form, identity activation, no bias, no split-half) beside the same four models' tower:
+    X^k[h] = sum_{i, j} W^k[h, i, j] X^{k-1}[i] * X^0[j] over the S + M embedded fields X^0, every map
+    sum-pooled over the embedding and projected by cin_res, its logit added to the tower's (after the cross
+    network's, the attentional interactions' and the CCPM branch's); parameters cin_layer_{k-1}
+    [H_{k-1} F, H_k] (row i F + j, H_0 = F) and cin_res [sum H_k, 1], the loss's L2 term on cin_res as on
+    cross_res; (): none.
     wide_optimizer: "adam" (the reference's one optimizer) or "ftrl" (wdl only): wdl_weights trained
     by TF1 FtrlOptimizer(wide_lr, learning_rate_power=-0.5, initial_accumulator_value=0.1,
     l1_regularization_strength=wide_l1, l2_regularization_strength=wide_l2), the loss's L2 term on
@@ -121,13 +128,14 @@ class ModelSpec:
     PNN_MAX_FIELDS, PNN_EMB = 64, (8, 16, 32)                      # csrc/pnn.hip
     BI_MAX_FIELDS, BI_MAX_EMB = 64, 64                             # csrc/bi.hip (E a multiple of 4)
     CCPM_MAX_LAYERS, CCPM_MAX_FILTERS, CCPM_MAX_FIELDS, CCPM_EMB = 3, 8, 64, (8, 16, 32)   # csrc/ccpm.hip
+    CIN_MAX_LAYERS, CIN_MAX_MAPS, CIN_MAX_FIELDS, CIN_EMB, CIN_MAX_WEIGHTS = 3, 64, 64, (8, 16, 32), 262144   # csrc/cin.hip
 
     def __init__(self, model, C=13, V=0, S=26, E=16, cate_index_size=1000, hidden=(400, 400, 400),
                  multi_ranges=(), Fw=0, lr=0.001, l2=1e-5, decay_steps=10000000, decay_rate=0.9,
                  beta1=0.9, beta2=0.999, eps=1e-8, logloss_eps=1e-7, tower="f32", dropout_keep_deep=None,
                  dropout_keep_fm=None, pos_weight=1.0, cross_layers=0, wide_optimizer="adam", wide_lr=None,
                  wide_l1=0.0, wide_l2=0.0, afm_attention=0, pnn=None, batch_norm=False, bn_eps=1e-5, bn_momentum=0.1,
-                 bi_interaction=False, ccpm_filters=()):
+                 bi_interaction=False, ccpm_filters=(), cin_layers=()):
         if model not in FAMILIES:
             raise ValueError("unsupported model %r" % model)
         if wide_optimizer not in ("adam", "ftrl"):
@@ -156,6 +164,14 @@ class ModelSpec:
         if not ok:
             raise ValueError("ccpm_filters must be a sequence of integers, got %r" % (ccpm_filters,))
         self.ccpm_filters = tuple(int(c) for c in filters)
+        try:
+            layers = tuple(cin_layers)
+            ok = all(int(h) == h for h in layers)
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise ValueError("cin_layers must be a sequence of integers, got %r" % (cin_layers,))
+        self.cin_layers = tuple(int(h) for h in layers)
         if pnn == "outer":
             raise ValueError("pnn='outer': the outer-product layer (PNN.py:85-91, an E * E first-layer input) is "
                              "not built; pnn='inner' is")
@@ -272,6 +288,19 @@ class ModelSpec:
                                  % (self.CCPM_MAX_LAYERS, self.CCPM_MAX_FILTERS, self.CCPM_MAX_FIELDS,
                                     " / ".join(map(str, self.CCPM_EMB)), self.ccpm_filters, F, self.E))
 
+        if self.cin_layers:
+            self._check_side_option("cin_layers", "the compressed interaction network joins", "the branch reads "
+                                    "the f32 tower input", "the branch reads the undropped fields")
+            Lc, F = len(self.cin_layers), self.afm_fields
+            if (Lc > self.CIN_MAX_LAYERS or not all(1 <= h <= self.CIN_MAX_MAPS for h in self.cin_layers)
+                    or not 2 <= F <= self.CIN_MAX_FIELDS or self.E not in self.CIN_EMB
+                    or self.cin_weights() > self.CIN_MAX_WEIGHTS):
+                raise ValueError("cin_layers: 1 to %d layers of 1 to %d feature maps on 2 to %d embedded fields of "
+                                 "size %s, at most %d layer weights; got %r on %d fields of size %d (%d weights)"
+                                 % (self.CIN_MAX_LAYERS, self.CIN_MAX_MAPS, self.CIN_MAX_FIELDS,
+                                    " / ".join(map(str, self.CIN_EMB)), self.CIN_MAX_WEIGHTS, self.cin_layers, F,
+                                    self.E, self.cin_weights()))
+
     def _check_side_option(self, opt, joins, reads_f32, reads_undropped):
         """The refusals every option on the tower input of the CROSS_MODELS shares, in that option's words."""
         if self.model not in self.CROSS_MODELS:
@@ -295,6 +324,11 @@ class ModelSpec:
         for c in self.ccpm_filters:
             out.append((out[-1][0] // 2, out[-1][1] // 2, c))
         return out
+
+    def cin_weights(self):
+        """The CIN's layer weights: sum_k H_k H_{k-1} F, H_0 = F."""
+        H = (self.afm_fields,) + self.cin_layers
+        return sum(H[k + 1] * H[k] * self.afm_fields for k in range(len(self.cin_layers)))
 
     @property
     def ftrl_lr(self):
@@ -486,6 +520,7 @@ class CTREngine:
         # the options only this class's own step carries
         for opt, on, why in (("bi_interaction", sp.bi_interaction, ""), ("cross_layers", sp.cross_layers, ""),
                              ("afm_attention", sp.afm_attention, ""), ("ccpm_filters", sp.ccpm_filters, ""),
+                             ("cin_layers", sp.cin_layers, ""),
                              ("pnn", sp.pnn, ""),
                              ("batch_norm", sp.batch_norm, " (the batch statistics would need a reduction across "
                                                            "the ranks)")):
@@ -722,6 +757,16 @@ class CTREngine:
                   partial(ccpm_unpack, shapes=shapes), ("adam/km", "adam/kv"))
             self.ccpm_f = (_lib.C.c_int32 * 3)(*self.ccpm)
             self.z_ccpm = z(B)
+        # compressed interaction network (ModelSpec.cin_layers, csrc/cin.hip): [c | W^1 | W^2 ..] and the logit
+        # z_cin [B] (the other branches' logits already added: the head's one z_extra).  L2 on c = cin_res, the
+        # output layer's CIN part, as on cross_res; nothing on the layer weights
+        self.cin = sp.cin_layers
+        if self.cin:
+            shapes = cin_shapes(sp.afm_fields, self.cin)
+            group("cin", sum(int(np.prod(shp)) for shp in shapes.values()), partial(cin_pack, shapes=shapes),
+                  partial(cin_unpack, shapes=shapes), ("adam/nm", "adam/nv"), reg=(sp.l2, sum(self.cin), self.opt[8:]))
+            self.cin_h = (_lib.C.c_int32 * 3)(*self.cin)
+            self.z_cin = z(B)
         # product layer (ModelSpec.pnn, csrc/pnn.hip): theta [D1, F]; lp itself is added into h[0] and kept
         # nowhere.  No regulariser (PNN.py:136-139 has none on it)
         self.pnn = sp.pnn
@@ -929,6 +974,16 @@ class CTREngine:
                     lim = math.sqrt(6.0 / (rf * (shp[-2] + shp[-1])))
                     P[k] = rng.uniform(-lim, lim, shp)
             self.groups["ccpm"].load(P)
+        if self.cin:
+            # cin_layer_* glorot-uniform (fan-in H_{k-1} F, fan-out H_k); cin_res ~ N(0, sqrt(2 / (sum H + 1))) as deep_res
+            P = {}
+            for k, shp in cin_shapes(sp.afm_fields, self.cin).items():
+                if k == "cin_res":
+                    P[k] = rng.standard_normal(shp) * math.sqrt(2.0 / (shp[0] + 1))
+                else:
+                    lim = math.sqrt(6.0 / (shp[0] + shp[1]))
+                    P[k] = rng.uniform(-lim, lim, shp)
+            self.groups["cin"].load(P)
         if self.pnn:
             # PNN.py:57: product-quadratic-inner ~ N(0, 0.01)
             v = rng.standard_normal((sp.hidden[0], sp.afm_fields)) * 0.01
@@ -1298,7 +1353,7 @@ class CTREngine:
         sp = self.spec
         if os.environ.get("DLAMD_FUSED_GATHER", "1") == "0" or not self.s3 or self.bf or sp.M:
             return False
-        if self.cross or self.afm or self.pnn or self.bi or self.ccpm:   # all read x0's deep columns, which the fused forms leave unwritten
+        if self.cross or self.afm or self.pnn or self.bi or self.ccpm or self.cin:   # all read x0's deep columns, which the fused forms leave unwritten
             return False
         if self.bn:   # the fused forms apply the ReLU themselves; layer 0 must store its pre-activation
             return False
@@ -1659,10 +1714,10 @@ class CTREngine:
                     self.head_blocks, sp.F, self._keep_thr(k1), self._keep_inv(k1), self._keep_thr(k2),
                     self._keep_inv(k2), self.seed & 0xFFFFFFFFFFFFFFFF, ptr(self.opt), ptr(self.fm_keep), s)
             return
-        if self.cross or self.afm or self.ccpm:
+        if self.cross or self.afm or self.ccpm or self.cin:
             # x0 is complete here (in lazy training the first layer's fused row gather wrote its
-            # deep columns): s and z_cross, z_afm (+ z_cross), z_ccpm (+ those), then the head with that
-            # extra logit
+            # deep columns): s and z_cross, z_afm (+ z_cross), z_ccpm (+ those), z_cin (+ those), then the
+            # head with that extra logit
             if self.cross:
                 self._c("cross_fwd", "dl_cross_fwd", B, self.D0, self.cross, ptr(self.x0), self.in_ld[0],
                         ptr(self.groups["cross"].w), ptr(self.cross_s), ptr(self.z_cross), s)
@@ -1675,6 +1730,10 @@ class CTREngine:
                 self._c("ccpm_fwd", "dl_ccpm_fwd", B, sp.afm_fields, sp.E, len(self.ccpm), self.ccpm_f, ptr(self.x0),
                         self.in_ld[0], self.cat_col, ptr(self.groups["ccpm"].w), ptr(z_extra), ptr(self.z_ccpm), s)
                 z_extra = self.z_ccpm
+            if self.cin:
+                self._c("cin_fwd", "dl_cin_fwd", B, sp.afm_fields, sp.E, len(self.cin), self.cin_h, ptr(self.x0),
+                        self.in_ld[0], self.cat_col, ptr(self.groups["cin"].w), ptr(z_extra), ptr(self.z_cin), s)
+                z_extra = self.z_cin
             self._c("head", "dl_head_fwd_bwd_cross" + sw, B, sp.fm_cols, H, ptr(self.fm_out), self.fm_ld,
                     ptr(self.h[-1]), self.h_ld[-1], ptr(self.w_head), ptr(self.in_label), sp.logloss_eps, *scale,
                     ptr(z_extra), ptr(self.score), ptr(self.z), ptr(self.dz),
@@ -1787,6 +1846,12 @@ class CTREngine:
             # the CCPM branch's share of dx0's field columns, likewise
             g = self.groups["ccpm"]
             self._c("ccpm_bwd", "dl_ccpm_bwd", B, sp.afm_fields, sp.E, len(self.ccpm), self.ccpm_f, ptr(self.x0),
+                    self.in_ld[0], self.cat_col, ptr(g.w), ptr(self.dz), ptr(self.dx0), self.dx_ld, 0,
+                    ptr(g.slab), g.blocks, s)
+        if self.cin:
+            # the compressed interaction network's share of dx0's field columns, likewise
+            g = self.groups["cin"]
+            self._c("cin_bwd", "dl_cin_bwd", B, sp.afm_fields, sp.E, len(self.cin), self.cin_h, ptr(self.x0),
                     self.in_ld[0], self.cat_col, ptr(g.w), ptr(self.dz), ptr(self.dx0), self.dx_ld, 0,
                     ptr(g.slab), g.blocks, s)
         if self.pnn:

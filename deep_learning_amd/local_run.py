@@ -33,6 +33,10 @@ ccpm_filters=C0,C1,.. (the same four models) adds the convolutional field intera
 test_model/CCPM.py beside the tower: per value a 3x3 convolution of that many filters with ReLU and a 2x2
 max-pool over the [embedding, field] map, then one more logit.
 
+cin_layers=H1,H2,.. (the same four models) adds xDeepFM's Compressed Interaction Network beside the tower:
+per value a layer of that many feature maps, each a learned sum of the element-wise products of the layer
+below's maps with the embedded fields; every map is summed over the embedding into one more logit.
+
 wide_optimizer=ftrl wide_lr=0.05 wide_l1=1e-3 wide_l2=0 (wdl: models/wdl.py reads them from its args)
 train the wide weights with FTRL-proximal instead of Adam; L1 leaves most wide rows at exactly zero.
 
@@ -108,6 +112,8 @@ class ModelParams:
                 self.bi_interaction = check_bi_interaction(v, self.alg_name)
             elif k == "ccpm_filters":     # the CCPM branch beside the tower, likewise
                 self.ccpm_filters = check_ccpm_filters(v, self.alg_name)
+            elif k == "cin_layers":       # the compressed interaction network beside the tower, likewise
+                self.cin_layers = check_cin_layers(v, self.alg_name)
             elif k in ("wide_optimizer", "wide_lr", "wide_l1", "wide_l2"):   # stored only when given, too
                 setattr(self, k, check_wide_option(k, v, self.alg_name))
             else:
@@ -117,6 +123,8 @@ class ModelParams:
         check_eval_options(getattr(self, "eval_metrics", None), getattr(self, "gauc_slot", None), self.cate_field_size)
         if hasattr(self, "ccpm_filters"):   # the map's limits, known now that the fields are counted
             check_ccpm_map(self.ccpm_filters, self.embedding_size, self.cate_field_size + self.multi_field_size)
+        if hasattr(self, "cin_layers"):     # likewise
+            check_cin_fields(self.cin_layers, self.embedding_size, self.cate_field_size + self.multi_field_size)
 
 
 EVAL_METRICS = ("auc", "gauc", "logloss", "calibration")
@@ -217,6 +225,36 @@ def check_ccpm_map(filters, E, F):
                          "least 1 x 1; got %d fields of size %d"
                          % (",".join(map(str, filters)), ModelSpec.CCPM_MAX_FIELDS,
                             " / ".join(map(str, ModelSpec.CCPM_EMB)), F, E))
+
+
+def check_cin_layers(v, alg_name):
+    """cin_layers=H1,H2,.. as a list of ints; refuses (SystemExit) anything but 1 to CIN_MAX_LAYERS integers
+    in [1, CIN_MAX_MAPS], and a model other than the dnn_* ones.  (The field count and the embedding size
+    are known only once the fields are counted: check_cin_fields refuses those.)"""
+    from .engine import ModelSpec
+    try:
+        h = [int(x) for x in v.split(",")]
+    except ValueError:
+        raise SystemExit("cin_layers=%s is not a comma-separated list of integers" % v)
+    if not 1 <= len(h) <= ModelSpec.CIN_MAX_LAYERS or not all(1 <= x <= ModelSpec.CIN_MAX_MAPS for x in h):
+        raise SystemExit("cin_layers=%s must hold 1 to %d values in [1, %d]"
+                         % (v, ModelSpec.CIN_MAX_LAYERS, ModelSpec.CIN_MAX_MAPS))
+    if alg_name not in ModelSpec.CROSS_MODELS:
+        raise SystemExit("cin_layers=%s: the compressed interaction network joins the tower of %s only, not %s"
+                         % (v, ", ".join(ModelSpec.CROSS_MODELS), alg_name))
+    return h
+
+
+def check_cin_fields(layers, E, F):
+    """Refuses (SystemExit) the F fields of size E the CIN does not take: what ModelSpec would."""
+    from .engine import ModelSpec
+    H = [F] + list(layers)
+    nw = sum(H[k + 1] * H[k] * F for k in range(len(layers)))
+    if E not in ModelSpec.CIN_EMB or not 2 <= F <= ModelSpec.CIN_MAX_FIELDS or nw > ModelSpec.CIN_MAX_WEIGHTS:
+        raise SystemExit("cin_layers=%s: 2 to %d embedded fields of size %s and at most %d layer weights; got %d "
+                         "fields of size %d (%d weights)"
+                         % (",".join(map(str, layers)), ModelSpec.CIN_MAX_FIELDS,
+                            " / ".join(map(str, ModelSpec.CIN_EMB)), ModelSpec.CIN_MAX_WEIGHTS, F, E, nw))
 
 
 def check_batch_norm(k, v):

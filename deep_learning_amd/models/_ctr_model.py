@@ -65,6 +65,8 @@ def _spec_from_args(model, args):
         kw.update(bi_interaction=bool(args.bi_interaction))
     if getattr(args, "ccpm_filters", None) is not None:    # local_run's ccpm_filters= (stored only when given)
         kw.update(ccpm_filters=tuple(int(c) for c in args.ccpm_filters))
+    if getattr(args, "cin_layers", None) is not None:      # local_run's cin_layers= (stored only when given)
+        kw.update(cin_layers=tuple(int(h) for h in args.cin_layers))
     return ModelSpec(model, **kw)
 
 

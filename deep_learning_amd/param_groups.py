@@ -1,5 +1,5 @@
 """The small dense parameter vectors beside the deep tower (cross network, attentional interactions,
-CCPM branch, product layer, batch norm's [gamma | beta]): their host layouts and their device life cycle.
+CCPM branch, compressed interaction network, product layer, batch norm's [gamma | beta]): their host layouts and their device life cycle.
 
 Every one of them is a flat f32 vector padded to 4 with two Adam moment vectors, a slab of per-block
 partial gradient sums [dl_<x>_grid(max_batch), n] its backward kernel fills, and one dl_adam_dense
@@ -100,6 +100,27 @@ def ccpm_pack(P, shapes):
 
 def ccpm_unpack(v, shapes):
     """Inverse of ccpm_pack: {key: numpy in the reference's shape}."""
+    return _shapes_unpack(v, shapes)
+
+
+def cin_shapes(F, layers):
+    """The CIN variables in the device vector's order [c | W^1 | W^2 ..]: cin_res [sum H_k, 1], then per
+    layer cin_layer_{k-1} [H_{k-1} F, H_k] (row i F + j; H_0 = F)."""
+    out = {"cin_res": (sum(layers), 1)}
+    H = (F,) + tuple(layers)
+    for k in range(len(layers)):
+        out["cin_layer_%d" % k] = (H[k] * F, H[k + 1])
+    return out
+
+
+def cin_pack(P, shapes):
+    """Reference-layout CIN parameters -> the device vector [c | W^1 | ..]; a variable of another size is
+    refused."""
+    return _shapes_pack(P, shapes, "cin_layers: ")
+
+
+def cin_unpack(v, shapes):
+    """Inverse of cin_pack: {key: numpy in the reference's shape}."""
     return _shapes_unpack(v, shapes)
 
 

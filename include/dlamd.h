@@ -637,6 +637,34 @@ int dl_ccpm_bwd(int32_t B, int32_t F, int32_t E, int32_t L, const int32_t* filte
                 int32_t x_col0, const float* params, const float* dz, float* dx0, int32_t dx_ld, int32_t dx_col0,
                 float* slab, int32_t slab_rows, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Compressed Interaction Network (xDeepFM, Lian et al. 2018, eq. 6-8; direct form, identity activation,
+ * no bias, no split-half) beside the dnn_* tower, on the F embedded fields of x0 [B, ld], field f in
+ * columns [x_col0 + f E, x_col0 + (f + 1) E).  With X^0 = the fields [F, E], H_0 = F, for the L layers
+ * of layers[k - 1] = H_k feature maps:
+ *   X^k[h, e] = sum_{i < H_{k-1}} sum_{j < F} W^k[h, i, j] X^{k-1}[i, e] X^0[j, e]
+ *   z_cin = sum_k sum_h c[off_k + h] sum_e X^k[h, e]
+ * params: [c (sum H_k) | W^1 | W^2 | ..], W^k stored [H_{k-1} F, H_k] (row i F + j, column h).
+ * 1 <= L <= 3, 1 <= H_k <= 64, 2 <= F <= 64, E one of 8, 16, 32, sum_k H_k H_{k-1} F <= 262,144;
+ * anything else is refused and nothing is written.  layers is a host array of L values.
+ * dl_cin_fwd writes z_out[b] = z_cin[b] + (z_add ? z_add[b] : 0) (z_add: the logit of the cross network,
+ * the attentional interactions and the CCPM branch, so the head's one z_extra carries all four).
+ * dl_cin_bwd recomputes the maps from x0, adds dX^0 INTO dx0 [B, dx_ld] columns
+ * [dx_col0, dx_col0 + F E) and leaves the batch sums of the parameter gradients as per-block partials
+ * slab[block][n] in the layout of params (dl_cin_grid(B) blocks, at most 128: at most 128 MB;
+ * dl_adam_dense sums them in slab order).  Every layer is a GEMM on the exact f32 MFMA whose operand
+ * X^{k-1}[i] * X^0[j] is formed in registers; no atomics: the same inputs give the same bits on every run. */
+int dl_cin_grid(int32_t B);
+int dl_cin_fwd(int32_t B, int32_t F, int32_t E, int32_t L, const int32_t* layers, const float* x0, int32_t ld,
+               int32_t x_col0, const float* params, const float* z_add, float* z_out, void* stream);
+int dl_cin_bwd(int32_t B, int32_t F, int32_t E, int32_t L, const int32_t* layers, const float* x0, int32_t ld,
+               int32_t x_col0, const float* params, const float* dz, float* dx0, int32_t dx_ld, int32_t dx_col0,
+               float* slab, int32_t slab_rows, void* stream);
+/* The f32 matrix-rate yardstick of scripts/cin_bench.py: `blocks` blocks of 4 waves, each wave 8 independent
+ * chains of `iters` v_mfma_f32_16x16x4_f32 (8 * 2048 * iters FLOP a wave, no memory traffic); out needs
+ * blocks * 256 floats (n_out is checked). */
+int dl_mfma_f32_probe(float* out, int64_t n_out, int32_t blocks, int32_t iters, void* stream);
+
 /* Wide&Deep cross logit, forward and backward fused (models/wdl.py:225-275):
  * z = sum_f w[wide_f] + sum_j w[Fw+j] h_j + bias[0] (w = wdl_weights [w_rows]; the
  * deep-output rows Fw..Fw+H alias wide ids); sigmoid + eps-log-loss as dl_head_fwd_bwd.

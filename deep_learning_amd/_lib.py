@@ -158,6 +158,9 @@ SIGNATURES = {
     "dl_cin_grid": (I32, [I32]),
     "dl_cin_fwd": (I32, [I32, I32, I32, I32, P, P, I32, I32, P, P, P, P]),
     "dl_cin_bwd": (I32, [I32, I32, I32, I32, P, P, I32, I32, P, P, P, I32, I32, P, I32, P]),
+    "dl_autoint_grid": (I32, [I32]),
+    "dl_autoint_fwd": (I32, [I32, I32, I32, I32, I32, I32, P, I32, I32, P, P, P, P]),
+    "dl_autoint_bwd": (I32, [I32, I32, I32, I32, I32, I32, P, I32, I32, P, P, P, I32, I32, P, I32, P]),
     "dl_afm_grid": (I32, [I32]),
     "dl_afm_fwd": (I32, [I32, I32, I32, I32, P, I32, I32, P, P, P, P, P]),
     "dl_afm_bwd": (I32, [I32, I32, I32, I32, P, I32, I32, P, P, P, P, I32, I32, P, I32, P]),

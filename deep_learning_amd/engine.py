@@ -31,10 +31,25 @@ import torch
 
 from . import _lib
 from ._lib import call, ptr
-from .param_groups import (BN_KEY, PNN_KEY, ParamGroup, _ru, afm_pack, afm_unpack, bn_pack, bn_unpack, bn_vec,
+from .param_groups import (BN_KEY, PNN_KEY, ParamGroup, _ru, afm_pack, afm_unpack, autoint_pack, autoint_shapes,
+                           autoint_unpack, bn_pack, bn_unpack, bn_vec,
                            ccpm_pack, ccpm_shapes, ccpm_unpack, cin_pack, cin_shapes, cin_unpack, cross_pack, cross_unpack, pnn_pack, pnn_unpack)
 
 F32 = torch.float32
+
+
+def autoint_refusal(L, Hn, D, F, E):
+    """Why csrc/autoint.hip does not take L interacting layers of Hn heads on D columns over F fields of
+    size E (ModelSpec raises it as a ValueError, local_run as a SystemExit), or None."""
+    M = ModelSpec
+    if (1 <= L <= M.AUTOINT_MAX_LAYERS and Hn in M.AUTOINT_HEADS and D in M.AUTOINT_DIMS and D // Hn >= 2
+            and 2 <= F <= M.AUTOINT_MAX_FIELDS and E in M.AUTOINT_EMB):
+        return None
+    return ("autoint_layers: 1 to %d layers of autoint_heads in %s on autoint_dim in %s columns with at least 2 a "
+            "head, on 2 to %d embedded fields of size %s; got autoint_layers=%d autoint_heads=%d autoint_dim=%d "
+            "on %d fields of size %d"
+            % (M.AUTOINT_MAX_LAYERS, " / ".join(map(str, M.AUTOINT_HEADS)), " / ".join(map(str, M.AUTOINT_DIMS)),
+               M.AUTOINT_MAX_FIELDS, " / ".join(map(str, M.AUTOINT_EMB)), L, Hn, D, F, E))
 
 
 # Model families of the reference's pipeline-style model files (SURVEY.md §8(a) A6-A25):
@@ -116,6 +131,13 @@ class ModelSpec:
     network's, the attentional interactions' and the CCPM branch's); parameters cin_layer_{k-1}
     [H_{k-1} F, H_k] (row i F + j, H_0 = F) and cin_res [sum H_k, 1], the loss's L2 term on cin_res as on
     cross_res; (): none.
+    autoint_layers, autoint_heads, autoint_dim: L stacked interacting layers of AutoInt (Song et al. 2019, eq.
+    5-8) beside the same four models' tower, Hn heads on D columns (d = D / Hn a head): with X^0 the S + M
+    embedded fields [F, E], X^l = relu(concat_h softmax(Q_h K_h^T) V_h + X^{l-1} Wr_l), Q, K, V = X^{l-1} Wq_l,
+    Wk_l, Wv_l (unscaled scores, no bias), X^L projected by autoint_res, its logit added to the tower's last
+    (after every other branch's); parameters autoint_{q,k,v,r}_{l-1} [D_{l-1}, D] (D_0 = E) and autoint_res
+    [F D, 1], the loss's L2 term on autoint_res as on cin_res; L in 1..3, Hn in 1 / 2 / 4, D in 8 / 16 / 32 with
+    D / Hn >= 2; autoint_layers=0 (the default, with heads 2 and dim 16): none.
     wide_optimizer: "adam" (the reference's one optimizer) or "ftrl" (wdl only): wdl_weights trained
     by TF1 FtrlOptimizer(wide_lr, learning_rate_power=-0.5, initial_accumulator_value=0.1,
     l1_regularization_strength=wide_l1, l2_regularization_strength=wide_l2), the loss's L2 term on
@@ -129,13 +151,15 @@ class ModelSpec:
     BI_MAX_FIELDS, BI_MAX_EMB = 64, 64                             # csrc/bi.hip (E a multiple of 4)
     CCPM_MAX_LAYERS, CCPM_MAX_FILTERS, CCPM_MAX_FIELDS, CCPM_EMB = 3, 8, 64, (8, 16, 32)   # csrc/ccpm.hip
     CIN_MAX_LAYERS, CIN_MAX_MAPS, CIN_MAX_FIELDS, CIN_EMB, CIN_MAX_WEIGHTS = 3, 64, 64, (8, 16, 32), 262144   # csrc/cin.hip
+    AUTOINT_MAX_LAYERS, AUTOINT_HEADS, AUTOINT_DIMS, AUTOINT_MAX_FIELDS, AUTOINT_EMB = 3, (1, 2, 4), (8, 16, 32), 64, (8, 16, 32)   # csrc/autoint.hip
 
     def __init__(self, model, C=13, V=0, S=26, E=16, cate_index_size=1000, hidden=(400, 400, 400),
                  multi_ranges=(), Fw=0, lr=0.001, l2=1e-5, decay_steps=10000000, decay_rate=0.9,
                  beta1=0.9, beta2=0.999, eps=1e-8, logloss_eps=1e-7, tower="f32", dropout_keep_deep=None,
                  dropout_keep_fm=None, pos_weight=1.0, cross_layers=0, wide_optimizer="adam", wide_lr=None,
                  wide_l1=0.0, wide_l2=0.0, afm_attention=0, pnn=None, batch_norm=False, bn_eps=1e-5, bn_momentum=0.1,
-                 bi_interaction=False, ccpm_filters=(), cin_layers=()):
+                 bi_interaction=False, ccpm_filters=(), cin_layers=(), autoint_layers=0, autoint_heads=2,
+                 autoint_dim=16):
         if model not in FAMILIES:
             raise ValueError("unsupported model %r" % model)
         if wide_optimizer not in ("adam", "ftrl"):
@@ -172,6 +196,11 @@ class ModelSpec:
         if not ok:
             raise ValueError("cin_layers must be a sequence of integers, got %r" % (cin_layers,))
         self.cin_layers = tuple(int(h) for h in layers)
+        for k, v in (("autoint_layers", autoint_layers), ("autoint_heads", autoint_heads),
+                     ("autoint_dim", autoint_dim)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise ValueError("autoint_layers: %s must be an integer, got %r" % (k, v))
+        self.autoint_layers, self.autoint_heads, self.autoint_dim = int(autoint_layers), int(autoint_heads), int(autoint_dim)
         if pnn == "outer":
             raise ValueError("pnn='outer': the outer-product layer (PNN.py:85-91, an E * E first-layer input) is "
                              "not built; pnn='inner' is")
@@ -300,6 +329,13 @@ class ModelSpec:
                                  % (self.CIN_MAX_LAYERS, self.CIN_MAX_MAPS, self.CIN_MAX_FIELDS,
                                     " / ".join(map(str, self.CIN_EMB)), self.CIN_MAX_WEIGHTS, self.cin_layers, F,
                                     self.E, self.cin_weights()))
+
+        if self.autoint_layers:   # 0: off, whatever the other two say
+            self._check_side_option("autoint_layers", "the interacting layers join", "the branch reads the f32 "
+                                    "tower input", "the branch reads the undropped fields")
+            why = autoint_refusal(self.autoint_layers, self.autoint_heads, self.autoint_dim, self.afm_fields, self.E)
+            if why:
+                raise ValueError(why)
 
     def _check_side_option(self, opt, joins, reads_f32, reads_undropped):
         """The refusals every option on the tower input of the CROSS_MODELS shares, in that option's words."""
@@ -520,7 +556,7 @@ class CTREngine:
         # the options only this class's own step carries
         for opt, on, why in (("bi_interaction", sp.bi_interaction, ""), ("cross_layers", sp.cross_layers, ""),
                              ("afm_attention", sp.afm_attention, ""), ("ccpm_filters", sp.ccpm_filters, ""),
-                             ("cin_layers", sp.cin_layers, ""),
+                             ("cin_layers", sp.cin_layers, ""), ("autoint_layers", sp.autoint_layers, ""),
                              ("pnn", sp.pnn, ""),
                              ("batch_norm", sp.batch_norm, " (the batch statistics would need a reduction across "
                                                            "the ranks)")):
@@ -767,6 +803,17 @@ class CTREngine:
                   partial(cin_unpack, shapes=shapes), ("adam/nm", "adam/nv"), reg=(sp.l2, sum(self.cin), self.opt[8:]))
             self.cin_h = (_lib.C.c_int32 * 3)(*self.cin)
             self.z_cin = z(B)
+        # AutoInt's interacting layers (ModelSpec.autoint_layers, csrc/autoint.hip): [w | Wq_1 | Wk_1 | Wv_1 |
+        # Wr_1 | Wq_2 ..] and the logit z_autoint [B] (the other branches' logits already added: the head's one
+        # z_extra); the backward recomputes in LDS and keeps nothing in HBM.  L2 on w = autoint_res, the output
+        # layer's AutoInt part, as on cin_res; nothing on the layer matrices
+        self.autoint = sp.autoint_layers
+        if self.autoint:
+            shapes = autoint_shapes(sp.afm_fields, sp.E, self.autoint, sp.autoint_dim)
+            group("autoint", sum(int(np.prod(shp)) for shp in shapes.values()), partial(autoint_pack, shapes=shapes),
+                  partial(autoint_unpack, shapes=shapes), ("adam/im", "adam/iv"),
+                  reg=(sp.l2, sp.afm_fields * sp.autoint_dim, self.opt[8:]))
+            self.z_autoint = z(B)
         # product layer (ModelSpec.pnn, csrc/pnn.hip): theta [D1, F]; lp itself is added into h[0] and kept
         # nowhere.  No regulariser (PNN.py:136-139 has none on it)
         self.pnn = sp.pnn
@@ -984,6 +1031,17 @@ class CTREngine:
                     lim = math.sqrt(6.0 / (shp[0] + shp[1]))
                     P[k] = rng.uniform(-lim, lim, shp)
             self.groups["cin"].load(P)
+        if self.autoint:
+            # autoint_{q,k,v,r}_* glorot-uniform (fan-in D_{l-1}, fan-out D); autoint_res ~ N(0, sqrt(2 / (F D + 1)))
+            # as deep_res
+            P = {}
+            for k, shp in autoint_shapes(sp.afm_fields, sp.E, self.autoint, sp.autoint_dim).items():
+                if k == "autoint_res":
+                    P[k] = rng.standard_normal(shp) * math.sqrt(2.0 / (shp[0] + 1))
+                else:
+                    lim = math.sqrt(6.0 / (shp[0] + shp[1]))
+                    P[k] = rng.uniform(-lim, lim, shp)
+            self.groups["autoint"].load(P)
         if self.pnn:
             # PNN.py:57: product-quadratic-inner ~ N(0, 0.01)
             v = rng.standard_normal((sp.hidden[0], sp.afm_fields)) * 0.01
@@ -1353,7 +1411,7 @@ class CTREngine:
         sp = self.spec
         if os.environ.get("DLAMD_FUSED_GATHER", "1") == "0" or not self.s3 or self.bf or sp.M:
             return False
-        if self.cross or self.afm or self.pnn or self.bi or self.ccpm or self.cin:   # all read x0's deep columns, which the fused forms leave unwritten
+        if self.cross or self.afm or self.pnn or self.bi or self.ccpm or self.cin or self.autoint:   # all read x0's deep columns, which the fused forms leave unwritten
             return False
         if self.bn:   # the fused forms apply the ReLU themselves; layer 0 must store its pre-activation
             return False
@@ -1714,10 +1772,10 @@ class CTREngine:
                     self.head_blocks, sp.F, self._keep_thr(k1), self._keep_inv(k1), self._keep_thr(k2),
                     self._keep_inv(k2), self.seed & 0xFFFFFFFFFFFFFFFF, ptr(self.opt), ptr(self.fm_keep), s)
             return
-        if self.cross or self.afm or self.ccpm or self.cin:
+        if self.cross or self.afm or self.ccpm or self.cin or self.autoint:
             # x0 is complete here (in lazy training the first layer's fused row gather wrote its
-            # deep columns): s and z_cross, z_afm (+ z_cross), z_ccpm (+ those), z_cin (+ those), then the
-            # head with that extra logit
+            # deep columns): s and z_cross, z_afm (+ z_cross), z_ccpm (+ those), z_cin (+ those), z_autoint
+            # (+ those), then the head with that extra logit
             if self.cross:
                 self._c("cross_fwd", "dl_cross_fwd", B, self.D0, self.cross, ptr(self.x0), self.in_ld[0],
                         ptr(self.groups["cross"].w), ptr(self.cross_s), ptr(self.z_cross), s)
@@ -1734,6 +1792,11 @@ class CTREngine:
                 self._c("cin_fwd", "dl_cin_fwd", B, sp.afm_fields, sp.E, len(self.cin), self.cin_h, ptr(self.x0),
                         self.in_ld[0], self.cat_col, ptr(self.groups["cin"].w), ptr(z_extra), ptr(self.z_cin), s)
                 z_extra = self.z_cin
+            if self.autoint:
+                self._c("autoint_fwd", "dl_autoint_fwd", B, sp.afm_fields, sp.E, self.autoint, sp.autoint_heads,
+                        sp.autoint_dim, ptr(self.x0), self.in_ld[0], self.cat_col, ptr(self.groups["autoint"].w),
+                        ptr(z_extra), ptr(self.z_autoint), s)
+                z_extra = self.z_autoint
             self._c("head", "dl_head_fwd_bwd_cross" + sw, B, sp.fm_cols, H, ptr(self.fm_out), self.fm_ld,
                     ptr(self.h[-1]), self.h_ld[-1], ptr(self.w_head), ptr(self.in_label), sp.logloss_eps, *scale,
                     ptr(z_extra), ptr(self.score), ptr(self.z), ptr(self.dz),
@@ -1854,6 +1917,12 @@ class CTREngine:
             self._c("cin_bwd", "dl_cin_bwd", B, sp.afm_fields, sp.E, len(self.cin), self.cin_h, ptr(self.x0),
                     self.in_ld[0], self.cat_col, ptr(g.w), ptr(self.dz), ptr(self.dx0), self.dx_ld, 0,
                     ptr(g.slab), g.blocks, s)
+        if self.autoint:
+            # the interacting layers' share of dx0's field columns, likewise
+            g = self.groups["autoint"]
+            self._c("autoint_bwd", "dl_autoint_bwd", B, sp.afm_fields, sp.E, self.autoint, sp.autoint_heads,
+                    sp.autoint_dim, ptr(self.x0), self.in_ld[0], self.cat_col, ptr(g.w), ptr(self.dz), ptr(self.dx0),
+                    self.dx_ld, 0, ptr(g.slab), g.blocks, s)
         if self.pnn:
             # the product layer's share, from the ReluGrad-masked dh[0] the tower's backward formed
             g = self.groups["pnn"]

@@ -37,6 +37,10 @@ cin_layers=H1,H2,.. (the same four models) adds xDeepFM's Compressed Interaction
 per value a layer of that many feature maps, each a learned sum of the element-wise products of the layer
 below's maps with the embedded fields; every map is summed over the embedding into one more logit.
 
+autoint_layers=L autoint_heads=Hn autoint_dim=D (the same four models; defaults 0, 2, 16; 0 layers: off) adds
+AutoInt's interacting layers beside the tower: L stacked layers of multi-head self-attention over the
+embedded fields (Hn heads on D columns) with a residual projection and a ReLU, then one more logit.
+
 wide_optimizer=ftrl wide_lr=0.05 wide_l1=1e-3 wide_l2=0 (wdl: models/wdl.py reads them from its args)
 train the wide weights with FTRL-proximal instead of Adam; L1 leaves most wide rows at exactly zero.
 
@@ -114,6 +118,8 @@ class ModelParams:
                 self.ccpm_filters = check_ccpm_filters(v, self.alg_name)
             elif k == "cin_layers":       # the compressed interaction network beside the tower, likewise
                 self.cin_layers = check_cin_layers(v, self.alg_name)
+            elif k in ("autoint_layers", "autoint_heads", "autoint_dim"):   # AutoInt's interacting layers, likewise
+                setattr(self, k, check_autoint_option(k, v, self.alg_name))
             elif k in ("wide_optimizer", "wide_lr", "wide_l1", "wide_l2"):   # stored only when given, too
                 setattr(self, k, check_wide_option(k, v, self.alg_name))
             else:
@@ -125,6 +131,9 @@ class ModelParams:
             check_ccpm_map(self.ccpm_filters, self.embedding_size, self.cate_field_size + self.multi_field_size)
         if hasattr(self, "cin_layers"):     # likewise
             check_cin_fields(self.cin_layers, self.embedding_size, self.cate_field_size + self.multi_field_size)
+        if getattr(self, "autoint_layers", 0):   # likewise; 0 is off, whatever the other two say
+            check_autoint_shape(self.autoint_layers, getattr(self, "autoint_heads", 2), getattr(self, "autoint_dim", 16),
+                                self.embedding_size, self.cate_field_size + self.multi_field_size)
 
 
 EVAL_METRICS = ("auc", "gauc", "logloss", "calibration")
@@ -255,6 +264,30 @@ def check_cin_fields(layers, E, F):
                          "fields of size %d (%d weights)"
                          % (",".join(map(str, layers)), ModelSpec.CIN_MAX_FIELDS,
                             " / ".join(map(str, ModelSpec.CIN_EMB)), ModelSpec.CIN_MAX_WEIGHTS, F, E, nw))
+
+
+def check_autoint_option(k, v, alg_name):
+    """autoint_layers=L, autoint_heads=Hn or autoint_dim=D as an int; refuses (SystemExit) anything but an
+    integer, and autoint_layers != 0 on a model other than the dnn_* ones.  (The accepted shapes depend on all
+    three and on the fields: check_autoint_shape refuses those once the fields are counted.)"""
+    from .engine import ModelSpec
+    try:
+        n = int(v)
+    except ValueError:
+        raise SystemExit("autoint_layers: %s=%s is not an integer" % (k, v))
+    if k == "autoint_layers" and n and alg_name not in ModelSpec.CROSS_MODELS:
+        raise SystemExit("autoint_layers=%s: the interacting layers join the tower of %s only, not %s"
+                         % (v, ", ".join(ModelSpec.CROSS_MODELS), alg_name))
+    return n
+
+
+def check_autoint_shape(L, Hn, D, E, F):
+    """Refuses (SystemExit) the layers, heads, columns and fields the interacting layers do not take: what
+    ModelSpec would."""
+    from .engine import autoint_refusal
+    why = autoint_refusal(L, Hn, D, F, E)
+    if why:
+        raise SystemExit(why)
 
 
 def check_batch_norm(k, v):

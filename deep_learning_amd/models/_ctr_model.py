@@ -67,6 +67,9 @@ def _spec_from_args(model, args):
         kw.update(ccpm_filters=tuple(int(c) for c in args.ccpm_filters))
     if getattr(args, "cin_layers", None) is not None:      # local_run's cin_layers= (stored only when given)
         kw.update(cin_layers=tuple(int(h) for h in args.cin_layers))
+    for k in ("autoint_layers", "autoint_heads", "autoint_dim"):   # local_run's autoint_*= (stored only when given)
+        if getattr(args, k, None) is not None:
+            kw[k] = int(getattr(args, k))
     return ModelSpec(model, **kw)
 
 

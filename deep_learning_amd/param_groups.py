@@ -1,5 +1,5 @@
 """The small dense parameter vectors beside the deep tower (cross network, attentional interactions,
-CCPM branch, compressed interaction network, product layer, batch norm's [gamma | beta]): their host layouts and their device life cycle.
+CCPM branch, compressed interaction network, AutoInt's interacting layers, product layer, batch norm's [gamma | beta]): their host layouts and their device life cycle.
 
 Every one of them is a flat f32 vector padded to 4 with two Adam moment vectors, a slab of per-block
 partial gradient sums [dl_<x>_grid(max_batch), n] its backward kernel fills, and one dl_adam_dense
@@ -121,6 +121,28 @@ def cin_pack(P, shapes):
 
 def cin_unpack(v, shapes):
     """Inverse of cin_pack: {key: numpy in the reference's shape}."""
+    return _shapes_unpack(v, shapes)
+
+
+def autoint_shapes(F, E, L, D):
+    """The AutoInt variables in the device vector's order [w | Wq_1 | Wk_1 | Wv_1 | Wr_1 | Wq_2 ..]:
+    autoint_res [F D, 1], then per layer autoint_q_{l-1}, autoint_k_{l-1}, autoint_v_{l-1}, autoint_r_{l-1}
+    [D_{l-1}, D] (D_0 = E, D_l = D)."""
+    out = {"autoint_res": (F * D, 1)}
+    for l in range(L):
+        for m in "qkvr":
+            out["autoint_%s_%d" % (m, l)] = (D if l else E, D)
+    return out
+
+
+def autoint_pack(P, shapes):
+    """Reference-layout AutoInt parameters -> the device vector [w | Wq_1 | ..]; a variable of another size
+    is refused."""
+    return _shapes_pack(P, shapes, "autoint_layers: ")
+
+
+def autoint_unpack(v, shapes):
+    """Inverse of autoint_pack: {key: numpy in the reference's shape}."""
     return _shapes_unpack(v, shapes)
 
 

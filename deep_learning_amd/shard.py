@@ -186,6 +186,7 @@ class ShardedCTREngine(CTREngine):
                 ("pnn", spec.pnn, "theta's gradient is not part of the flat all-reduce"),
                 ("ccpm_filters", spec.ccpm_filters, "the convolution parameters' " + flat),
                 ("cin_layers", spec.cin_layers, "the interaction network's parameters' " + flat),
+                ("autoint_layers", spec.autoint_layers, "the interacting layers' parameters' " + flat),
                 ("bi_interaction", spec.bi_interaction, "its step does not launch the pooling's kernels around the "
                                                         "first tower layer"),
                 ("batch_norm", spec.batch_norm, "the batch statistics would need a reduction across the ranks")):

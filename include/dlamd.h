@@ -665,6 +665,31 @@ int dl_cin_bwd(int32_t B, int32_t F, int32_t E, int32_t L, const int32_t* layers
  * blocks * 256 floats (n_out is checked). */
 int dl_mfma_f32_probe(float* out, int64_t n_out, int32_t blocks, int32_t iters, void* stream);
 
+/* ------------------------------------------------------------------------
+ * AutoInt's interacting layers (Song et al. 2019, eq. 5-8) beside the dnn_* tower, on the F embedded fields
+ * of x0 [B, ld], field f in columns [x_col0 + f E, x_col0 + (f + 1) E).  With X^0 = the fields [F, E],
+ * D_0 = E, D_l = D, d = D / heads, for l = 1 .. L and X = X^{l-1}:
+ *   Q = X Wq_l, K = X Wk_l, V = X Wv_l, R = X Wr_l   ([F, D]; W*_l [D_{l-1}, D] row-major, no bias)
+ *   per head h (columns h d .. h d + d - 1): A_h = softmax_k(Q_h[i] . K_h[k]) (unscaled), O_h = A_h V_h
+ *   X^l = relu(O + R)        z_autoint = sum_{f, c} w[f D + c] X^L[f, c]
+ * params: [w (F D) | Wq_1 | Wk_1 | Wv_1 | Wr_1 | Wq_2 | ..].
+ * 1 <= L <= 3, heads one of 1, 2, 4, D one of 8, 16, 32 with D / heads >= 2, 2 <= F <= 64, E one of 8, 16,
+ * 32; anything else is refused and nothing is written.
+ * dl_autoint_fwd writes z_out[b] = z_autoint[b] + (z_add ? z_add[b] : 0) (z_add: the logit of the branches
+ * before it, so the head's one z_extra carries them all).
+ * dl_autoint_bwd recomputes the layers from x0 (in LDS: no workspace), adds dX^0 INTO dx0 [B, dx_ld] columns
+ * [dx_col0, dx_col0 + F E) and leaves the batch sums of the parameter gradients as per-block partials
+ * slab[block][n] in the layout of params (dl_autoint_grid(B) blocks, at most 512: at most 30 MB;
+ * dl_adam_dense sums them in slab order).  The projections and their gradients run on the exact f32 MFMA,
+ * the attention on the vector unit with an online softmax; no atomics: the same inputs give the same bits
+ * on every run. */
+int dl_autoint_grid(int32_t B);
+int dl_autoint_fwd(int32_t B, int32_t F, int32_t E, int32_t L, int32_t heads, int32_t D, const float* x0, int32_t ld,
+                   int32_t x_col0, const float* params, const float* z_add, float* z_out, void* stream);
+int dl_autoint_bwd(int32_t B, int32_t F, int32_t E, int32_t L, int32_t heads, int32_t D, const float* x0, int32_t ld,
+                   int32_t x_col0, const float* params, const float* dz, float* dx0, int32_t dx_ld, int32_t dx_col0,
+                   float* slab, int32_t slab_rows, void* stream);
+
 /* Wide&Deep cross logit, forward and backward fused (models/wdl.py:225-275):
  * z = sum_f w[wide_f] + sum_j w[Fw+j] h_j + bias[0] (w = wdl_weights [w_rows]; the
  * deep-output rows Fw..Fw+H alias wide ids); sigmoid + eps-log-loss as dl_head_fwd_bwd.

@@ -145,6 +145,8 @@ class ModelSpec:
     """
 
     CROSS_MODELS = ("dnn_pipeline", "dnn_cate", "dnn_multi", "dnn_multi_cate")
+    MAX_SLOTS, MAX_FM_CONT, REC_FWD_MAX_FM = 128, 32, 64     # csrc/embed.hip: kMaxSlots, kMaxHotCont, dl_embed_fwd_rec_flat
+    MAX_FM_COLS = 128                                        # csrc/head.hip: kHeadMaxFm
     CROSS_MAX_LAYERS, CROSS_MAX_IN = 4, 1024     # csrc/cross.hip
     AFM_MAX_ATT, AFM_MAX_FIELDS, AFM_EMB = 32, 64, (8, 16, 32)     # csrc/afm.hip
     PNN_MAX_FIELDS, PNN_EMB = 64, (8, 16, 32)                      # csrc/pnn.hip
@@ -228,6 +230,18 @@ class ModelSpec:
         self.hidden = list(hidden)
         self.multi_ranges = [list(r) for r in multi_ranges] if fam["multi"] else []
         self.Fw = Fw
+        # the lookup kernels' field limits (csrc/embed.hip check_layout, launch_embed_fwd), which the
+        # library itself reports only at the first launch
+        if self.fm_cont and self.C > self.MAX_FM_CONT:
+            raise ValueError("C=%d: at most %d FM cont fields (the embedding backward keeps their rows in "
+                             "registers)" % (self.C, self.MAX_FM_CONT))
+        slots = (self.C if self.fm_cont else 0) + 2 * S if self.fm else S
+        if slots > self.MAX_SLOTS:
+            raise ValueError("too many fields per sample for the embedding lookup: %d slots (%s), at most %d"
+                             % (slots, "FM cont + 2 * single cate" if self.fm else "single cate", self.MAX_SLOTS))
+        if self.fm_cols > self.MAX_FM_COLS:
+            raise ValueError("too many FM columns for the output layer: %d FM fields + E=%d second-order columns "
+                             "= %d, at most %d" % (self.F, E, self.fm_cols, self.MAX_FM_COLS))
         self.lr, self.l2 = lr, l2
         self.decay_steps, self.decay_rate = decay_steps, decay_rate
         self.beta1, self.beta2, self.eps, self.logloss_eps = beta1, beta2, eps, logloss_eps
@@ -1575,9 +1589,11 @@ class CTREngine:
             if fused and self.fused_gather_tab(B):
                 fused = "tab"
             self.plane_lookup(B, x0, s, deep=not fused, gtab=self.gtab if fused == "tab" else None)
-        elif not train and self.lazy and not sp.M and self.since_flush == 0 and type(self) is CTREngine:
+        elif (not train and self.lazy and not sp.M and self.since_flush == 0 and type(self) is CTREngine
+              and sp.F <= sp.REC_FWD_MAX_FM):
             # predict on a flushed table (every record caught up to the current step): the plain
-            # lookup, each reference reading its record's first line (dl_embed_fwd_rec_flat)
+            # lookup, each reference reading its record's first line (dl_embed_fwd_rec_flat; it
+            # takes at most 64 FM fields: wider models go through the gather + indexed lookup below)
             if self.n_rep:   # the replicated FM cont-field rows, compact
                 self._c("rec_gather", "dl_rec_gather", C_ref(L), ptr(self.rec), self.rec_ld, self.rec_flags, self.n_rep,
                         ptr(self.idx_uniq), None, 0, 1, ptr(self.hist), self.hist_len, ptr(self.opt), 0,

@@ -25,31 +25,18 @@ import math
 import os
 import time
 from functools import partial
+from types import SimpleNamespace
 
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, branches
 from ._lib import call, ptr
-from .param_groups import (BN_KEY, PNN_KEY, ParamGroup, _ru, afm_pack, afm_unpack, autoint_pack, autoint_shapes,
-                           autoint_unpack, bn_pack, bn_unpack, bn_vec,
-                           ccpm_pack, ccpm_shapes, ccpm_unpack, cin_pack, cin_shapes, cin_unpack, cross_pack, cross_unpack, pnn_pack, pnn_unpack)
+from .branches import BRANCHES, SIDE_MODELS
+from .param_groups import BN_KEY, ParamGroup, _ru, bn_pack, bn_unpack, bn_vec
+from .param_groups import ccpm_pack, ccpm_shapes, ccpm_unpack  # noqa: F401  (read from here outside the package)
 
 F32 = torch.float32
-
-
-def autoint_refusal(L, Hn, D, F, E):
-    """Why csrc/autoint.hip does not take L interacting layers of Hn heads on D columns over F fields of
-    size E (ModelSpec raises it as a ValueError, local_run as a SystemExit), or None."""
-    M = ModelSpec
-    if (1 <= L <= M.AUTOINT_MAX_LAYERS and Hn in M.AUTOINT_HEADS and D in M.AUTOINT_DIMS and D // Hn >= 2
-            and 2 <= F <= M.AUTOINT_MAX_FIELDS and E in M.AUTOINT_EMB):
-        return None
-    return ("autoint_layers: 1 to %d layers of autoint_heads in %s on autoint_dim in %s columns with at least 2 a "
-            "head, on 2 to %d embedded fields of size %s; got autoint_layers=%d autoint_heads=%d autoint_dim=%d "
-            "on %d fields of size %d"
-            % (M.AUTOINT_MAX_LAYERS, " / ".join(map(str, M.AUTOINT_HEADS)), " / ".join(map(str, M.AUTOINT_DIMS)),
-               M.AUTOINT_MAX_FIELDS, " / ".join(map(str, M.AUTOINT_EMB)), L, Hn, D, F, E))
 
 
 # Model families of the reference's pipeline-style model files (SURVEY.md §8(a) A6-A25):
@@ -144,16 +131,13 @@ class ModelSpec:
     wdl_weights dropped; wide_lr None: lr, and never decayed.
     """
 
-    CROSS_MODELS = ("dnn_pipeline", "dnn_cate", "dnn_multi", "dnn_multi_cate")
     MAX_SLOTS, MAX_FM_CONT, REC_FWD_MAX_FM = 128, 32, 64     # csrc/embed.hip: kMaxSlots, kMaxHotCont, dl_embed_fwd_rec_flat
     MAX_FM_COLS = 128                                        # csrc/head.hip: kHeadMaxFm
-    CROSS_MAX_LAYERS, CROSS_MAX_IN = 4, 1024     # csrc/cross.hip
-    AFM_MAX_ATT, AFM_MAX_FIELDS, AFM_EMB = 32, 64, (8, 16, 32)     # csrc/afm.hip
-    PNN_MAX_FIELDS, PNN_EMB = 64, (8, 16, 32)                      # csrc/pnn.hip
-    BI_MAX_FIELDS, BI_MAX_EMB = 64, 64                             # csrc/bi.hip (E a multiple of 4)
-    CCPM_MAX_LAYERS, CCPM_MAX_FILTERS, CCPM_MAX_FIELDS, CCPM_EMB = 3, 8, 64, (8, 16, 32)   # csrc/ccpm.hip
-    CIN_MAX_LAYERS, CIN_MAX_MAPS, CIN_MAX_FIELDS, CIN_EMB, CIN_MAX_WEIGHTS = 3, 64, 64, (8, 16, 32), 262144   # csrc/cin.hip
-    AUTOINT_MAX_LAYERS, AUTOINT_HEADS, AUTOINT_DIMS, AUTOINT_MAX_FIELDS, AUTOINT_EMB = 3, (1, 2, 4), (8, 16, 32), 64, (8, 16, 32)   # csrc/autoint.hip
+    # the side options' limits live beside their refusals (branches.py); the names read outside the package
+    CROSS_MODELS = SIDE_MODELS
+    AFM_MAX_ATT, AFM_MAX_FIELDS = branches.AFM_MAX_ATT, branches.AFM_MAX_FIELDS
+    CCPM_MAX_LAYERS, CCPM_MAX_FILTERS, CCPM_MAX_FIELDS = branches.CCPM_MAX_LAYERS, branches.CCPM_MAX_FILTERS, branches.CCPM_MAX_FIELDS
+    CIN_MAX_LAYERS, CIN_MAX_MAPS, CIN_MAX_FIELDS, CIN_MAX_WEIGHTS = branches.CIN_MAX_LAYERS, branches.CIN_MAX_MAPS, branches.CIN_MAX_FIELDS, branches.CIN_MAX_WEIGHTS
 
     def __init__(self, model, C=13, V=0, S=26, E=16, cate_index_size=1000, hidden=(400, 400, 400),
                  multi_ranges=(), Fw=0, lr=0.001, l2=1e-5, decay_steps=10000000, decay_rate=0.9,
@@ -162,6 +146,7 @@ class ModelSpec:
                  wide_l1=0.0, wide_l2=0.0, afm_attention=0, pnn=None, batch_norm=False, bn_eps=1e-5, bn_momentum=0.1,
                  bi_interaction=False, ccpm_filters=(), cin_layers=(), autoint_layers=0, autoint_heads=2,
                  autoint_dim=16):
+        given = locals()      # the keywords by name, for the side options' table
         if model not in FAMILIES:
             raise ValueError("unsupported model %r" % model)
         if wide_optimizer not in ("adam", "ftrl"):
@@ -176,46 +161,9 @@ class ModelSpec:
         self.wide_optimizer = wide_optimizer
         self.wide_lr = None if wide_lr is None else float(wide_lr)
         self.wide_l1, self.wide_l2 = float(wide_l1), float(wide_l2)
-        if int(cross_layers) != cross_layers or cross_layers < 0:
-            raise ValueError("cross_layers must be an integer >= 0, got %r" % (cross_layers,))
-        self.cross_layers = int(cross_layers)
-        if int(afm_attention) != afm_attention or afm_attention < 0:
-            raise ValueError("afm_attention must be an integer >= 0, got %r" % (afm_attention,))
-        self.afm_attention = int(afm_attention)
-        try:
-            filters = tuple(ccpm_filters)
-            ok = all(int(c) == c for c in filters)
-        except (TypeError, ValueError):
-            ok = False
-        if not ok:
-            raise ValueError("ccpm_filters must be a sequence of integers, got %r" % (ccpm_filters,))
-        self.ccpm_filters = tuple(int(c) for c in filters)
-        try:
-            layers = tuple(cin_layers)
-            ok = all(int(h) == h for h in layers)
-        except (TypeError, ValueError):
-            ok = False
-        if not ok:
-            raise ValueError("cin_layers must be a sequence of integers, got %r" % (cin_layers,))
-        self.cin_layers = tuple(int(h) for h in layers)
-        for k, v in (("autoint_layers", autoint_layers), ("autoint_heads", autoint_heads),
-                     ("autoint_dim", autoint_dim)):
-            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
-                raise ValueError("autoint_layers: %s must be an integer, got %r" % (k, v))
-        self.autoint_layers, self.autoint_heads, self.autoint_dim = int(autoint_layers), int(autoint_heads), int(autoint_dim)
-        if pnn == "outer":
-            raise ValueError("pnn='outer': the outer-product layer (PNN.py:85-91, an E * E first-layer input) is "
-                             "not built; pnn='inner' is")
-        if pnn not in (None, "inner"):
-            raise ValueError("pnn must be None or 'inner', got %r" % (pnn,))
-        self.pnn = pnn
-        self.batch_norm = bool(batch_norm)
-        self.bi_interaction = bool(bi_interaction)
-        self.bn_eps, self.bn_momentum = float(bn_eps), float(bn_momentum)
-        if not (math.isfinite(self.bn_eps) and self.bn_eps > 0.0):
-            raise ValueError("batch_norm: bn_eps must be finite and > 0, got %r" % (bn_eps,))
-        if not 0.0 < self.bn_momentum <= 1.0:
-            raise ValueError("batch_norm: bn_momentum must lie in (0, 1], got %r" % (bn_momentum,))
+        for b in BRANCHES:      # the side options' keywords, as their descriptors coerce them
+            for k, v in zip(b.keywords, b.coerce(*(given[k] for k in b.keywords))):
+                setattr(self, k, v)
         pos_weight = float(pos_weight)
         if not (math.isfinite(pos_weight) and pos_weight > 0.0):
             raise ValueError("pos_weight must be finite and > 0, got %r" % (pos_weight,))
@@ -268,34 +216,19 @@ class ModelSpec:
                 raise ValueError("dropout_keep_fm values must lie in (0, 1], got %r" % (keep,))
             dropout_keep_fm = keep if fam["fm"] and any(k < 1.0 for k in keep) else None
         self.dropout_keep_fm = dropout_keep_fm
-        if self.cross_layers:
-            self._check_side_option("cross_layers", "the cross network joins", "the cross network reads the f32 "
-                                    "tower input", "the cross network reads the undropped input")
-            if self.cross_layers > self.CROSS_MAX_LAYERS or self.deep_in > self.CROSS_MAX_IN:
-                raise ValueError("cross_layers: at most %d layers on at most %d tower-input columns, got %d on %d"
-                                 % (self.CROSS_MAX_LAYERS, self.CROSS_MAX_IN, self.cross_layers, self.deep_in))
-        if self.afm_attention:
-            self._check_side_option("afm_attention", "the attentional interactions join", "the branch reads the "
-                                    "f32 tower input", "the branch reads the undropped fields")
-            if (self.afm_attention > self.AFM_MAX_ATT or not 2 <= self.afm_fields <= self.AFM_MAX_FIELDS
-                    or self.E not in self.AFM_EMB):
-                raise ValueError("afm_attention: at most %d attention units on 2 to %d embedded fields of size %s, "
-                                 "got %d on %d fields of size %d"
-                                 % (self.AFM_MAX_ATT, self.AFM_MAX_FIELDS, " / ".join(map(str, self.AFM_EMB)),
-                                    self.afm_attention, self.afm_fields, self.E))
-        if self.pnn:
-            self._check_side_option("pnn", "the product layer feeds", "the product layer reads the f32 tower "
-                                    "input and finishes the f32 first layer", "the product layer reads the "
-                                    "undropped fields")
-            if self.dropout and self.dropout[1] < 1.0:
-                raise ValueError("pnn: not supported with dropout on the first layer's output "
-                                 "(dropout_keep_deep[1] < 1: that layer's ReLU and dropout live in the GEMM "
-                                 "epilogue the product layer replaces)")
-            if not 2 <= self.afm_fields <= self.PNN_MAX_FIELDS or self.E not in self.PNN_EMB:
-                raise ValueError("pnn: 2 to %d embedded fields of size %s, got %d fields of size %d"
-                                 % (self.PNN_MAX_FIELDS, " / ".join(map(str, self.PNN_EMB)), self.afm_fields,
-                                    self.E))
-
+        for b in BRANCHES:
+            values = b.values(self)
+            if not values[0]:
+                continue
+            if b.phrases:
+                self._check_side_option(b.name, *b.phrases)
+            why = b.refusal and b.refusal(self.afm_fields, self.E, self.deep_in, *values)
+            if why:
+                raise ValueError("%s: %s" % (b.name, why))
+        if self.pnn and self.dropout and self.dropout[1] < 1.0:
+            raise ValueError("pnn: not supported with dropout on the first layer's output "
+                             "(dropout_keep_deep[1] < 1: that layer's ReLU and dropout live in the GEMM "
+                             "epilogue the product layer replaces)")
         if self.batch_norm:
             if tower == "bf16":
                 raise ValueError("batch_norm: not supported with tower='bf16' (the normalisation finishes the "
@@ -308,54 +241,11 @@ class ModelSpec:
                 raise ValueError("batch_norm: not supported together with pnn (both finish layer 0's stored "
                                  "pre-activation in place)")
 
-        if self.bi_interaction:
-            self._check_side_option("bi_interaction", "the Bi-Interaction pooling feeds", "the pooling reads and "
-                                    "extends the f32 tower input", "the pooling's backward reads the undropped "
-                                    "fields")
-            if (not 2 <= self.afm_fields <= self.BI_MAX_FIELDS or self.E % 4
-                    or not 4 <= self.E <= self.BI_MAX_EMB):
-                raise ValueError("bi_interaction: 2 to %d embedded fields of a size that is a multiple of 4 in "
-                                 "[4, %d], got %d fields of size %d"
-                                 % (self.BI_MAX_FIELDS, self.BI_MAX_EMB, self.afm_fields, self.E))
-
-        if self.ccpm_filters:
-            self._check_side_option("ccpm_filters", "the convolutional interactions join", "the branch reads the "
-                                    "f32 tower input", "the branch reads the undropped fields")
-            Lc, F = len(self.ccpm_filters), self.afm_fields
-            if (Lc > self.CCPM_MAX_LAYERS or not all(1 <= c <= self.CCPM_MAX_FILTERS for c in self.ccpm_filters)
-                    or not 2 <= F <= self.CCPM_MAX_FIELDS or self.E not in self.CCPM_EMB
-                    or (F >> Lc) < 1 or (self.E >> Lc) < 1):
-                raise ValueError("ccpm_filters: 1 to %d layers of 1 to %d filters on 2 to %d embedded fields of "
-                                 "size %s, every layer halving the map to at least 1 x 1; got %r on %d fields "
-                                 "of size %d"
-                                 % (self.CCPM_MAX_LAYERS, self.CCPM_MAX_FILTERS, self.CCPM_MAX_FIELDS,
-                                    " / ".join(map(str, self.CCPM_EMB)), self.ccpm_filters, F, self.E))
-
-        if self.cin_layers:
-            self._check_side_option("cin_layers", "the compressed interaction network joins", "the branch reads "
-                                    "the f32 tower input", "the branch reads the undropped fields")
-            Lc, F = len(self.cin_layers), self.afm_fields
-            if (Lc > self.CIN_MAX_LAYERS or not all(1 <= h <= self.CIN_MAX_MAPS for h in self.cin_layers)
-                    or not 2 <= F <= self.CIN_MAX_FIELDS or self.E not in self.CIN_EMB
-                    or self.cin_weights() > self.CIN_MAX_WEIGHTS):
-                raise ValueError("cin_layers: 1 to %d layers of 1 to %d feature maps on 2 to %d embedded fields of "
-                                 "size %s, at most %d layer weights; got %r on %d fields of size %d (%d weights)"
-                                 % (self.CIN_MAX_LAYERS, self.CIN_MAX_MAPS, self.CIN_MAX_FIELDS,
-                                    " / ".join(map(str, self.CIN_EMB)), self.CIN_MAX_WEIGHTS, self.cin_layers, F,
-                                    self.E, self.cin_weights()))
-
-        if self.autoint_layers:   # 0: off, whatever the other two say
-            self._check_side_option("autoint_layers", "the interacting layers join", "the branch reads the f32 "
-                                    "tower input", "the branch reads the undropped fields")
-            why = autoint_refusal(self.autoint_layers, self.autoint_heads, self.autoint_dim, self.afm_fields, self.E)
-            if why:
-                raise ValueError(why)
-
     def _check_side_option(self, opt, joins, reads_f32, reads_undropped):
-        """The refusals every option on the tower input of the CROSS_MODELS shares, in that option's words."""
-        if self.model not in self.CROSS_MODELS:
+        """The refusals every option on the tower input of the SIDE_MODELS shares, in that option's words."""
+        if self.model not in SIDE_MODELS:
             raise ValueError("%s: %s the tower of %s only, not %s"
-                             % (opt, joins, ", ".join(self.CROSS_MODELS), self.model))
+                             % (opt, joins, ", ".join(SIDE_MODELS), self.model))
         if self.tower == "bf16":
             raise ValueError("%s: not supported with tower='bf16' (%s)" % (opt, reads_f32))
         if self.dropout and self.dropout[0] < 1.0:
@@ -377,8 +267,7 @@ class ModelSpec:
 
     def cin_weights(self):
         """The CIN's layer weights: sum_k H_k H_{k-1} F, H_0 = F."""
-        H = (self.afm_fields,) + self.cin_layers
-        return sum(H[k + 1] * H[k] * self.afm_fields for k in range(len(self.cin_layers)))
+        return branches.cin_weights(self.afm_fields, self.cin_layers)
 
     @property
     def ftrl_lr(self):
@@ -567,15 +456,8 @@ class CTREngine:
         if self.fmdrop and type(self) is not CTREngine:
             raise ValueError("dropout_keep_fm: not supported by %s (the mask is indexed by the local "
                              "row number; a sharded batch needs global rows)" % type(self).__name__)
-        # the options only this class's own step carries
-        for opt, on, why in (("bi_interaction", sp.bi_interaction, ""), ("cross_layers", sp.cross_layers, ""),
-                             ("afm_attention", sp.afm_attention, ""), ("ccpm_filters", sp.ccpm_filters, ""),
-                             ("cin_layers", sp.cin_layers, ""), ("autoint_layers", sp.autoint_layers, ""),
-                             ("pnn", sp.pnn, ""),
-                             ("batch_norm", sp.batch_norm, " (the batch statistics would need a reduction across "
-                                                           "the ranks)")):
-            if on and type(self) is not CTREngine:
-                raise ValueError("%s: not supported by %s%s" % (opt, type(self).__name__, why))
+        if type(self) is not CTREngine:      # the side options only this class's own step carries
+            branches.unsupported(sp, type(self).__name__)
         self.dev = torch.device(device)
         self.B = max_batch
         # set later: predict's planes (flush(planes=True)) and the step they were written at,
@@ -773,73 +655,32 @@ class CTREngine:
             self.fm_drop_desc = _lib.FmDrop(fm_keep=self.fm_keep.data_ptr(), inv1=self._keep_inv(self.fmdrop[0]),
                                             inv2=self._keep_inv(self.fmdrop[1]))
         self.score, self.z, self.dz = z(B), z(B), z(B)
-        # the branches' dense parameter vectors, each with its Adam moments and the backward's per-block
-        # partial sums (param_groups.py), in the order of their Adam launches; the enabled ones only
-        self.groups = {}
-
-        def group(name, n, pack, unpack, ckpt_keys, **kw):
-            self.groups[name] = ParamGroup(name, n, "dl_%s_grid" % name, B, dev, pack, unpack, ckpt_keys, **kw)
-        # cross network (ModelSpec.cross_layers, csrc/cross.hip): [c | w_0 .. | b_0 ..] in x0's column
-        # order, the forward's s [B, L] and z_cross [B].  L2 on c, the output layer's cross part (DCN.py:104:
-        # the whole projection), its sum of squares joining the head's in the step's regulariser sum
-        self.cross = Lc = sp.cross_layers
-        if self.cross:
-            D0, rows = self.D0, sp.x0_ref_rows()
-            lay = dict(L=Lc, D0=D0, rows=rows)
-            group("cross", (2 * Lc + 1) * D0, partial(cross_pack, **lay), partial(cross_unpack, **lay),
-                  ("adam/cm", "adam/cv"), reg=(sp.l2, D0, self.opt[8:]))
-            self.cross_s, self.z_cross = z(B, self.cross), z(B)
-        # attentional interactions (ModelSpec.afm_attention, csrc/afm.hip): [p (E) | h (A) | b (A) | W (E A)],
-        # the forward's softmax statistics [B, 2] and logit z_afm [B] (z_cross already added when both
-        # branches are on: the head's one z_extra).  No regulariser (AFM.py:137 has none on these variables)
-        self.afm = A = sp.afm_attention
-        if self.afm:
-            group("afm", E + 2 * A + E * A, partial(afm_pack, E=E, A=A), partial(afm_unpack, E=E, A=A),
-                  ("adam/am", "adam/av"))
-            self.afm_stats, self.z_afm = z(B, 2), z(B)
-        # CCPM branch (ModelSpec.ccpm_filters, csrc/ccpm.hip): [p | K_0 | b_0 | K_1 | b_1 ..] and the logit
-        # z_ccpm [B] (z_afm or z_cross already added when those branches are on: the head's one z_extra).
-        # No regulariser (CCPM.py:73-74: the loss is the log-loss alone)
-        self.ccpm = sp.ccpm_filters
-        if self.ccpm:
-            shapes = ccpm_shapes(sp.ccpm_dims())
-            group("ccpm", sum(int(np.prod(shp)) for shp in shapes.values()), partial(ccpm_pack, shapes=shapes),
-                  partial(ccpm_unpack, shapes=shapes), ("adam/km", "adam/kv"))
-            self.ccpm_f = (_lib.C.c_int32 * 3)(*self.ccpm)
-            self.z_ccpm = z(B)
-        # compressed interaction network (ModelSpec.cin_layers, csrc/cin.hip): [c | W^1 | W^2 ..] and the logit
-        # z_cin [B] (the other branches' logits already added: the head's one z_extra).  L2 on c = cin_res, the
-        # output layer's CIN part, as on cross_res; nothing on the layer weights
-        self.cin = sp.cin_layers
-        if self.cin:
-            shapes = cin_shapes(sp.afm_fields, self.cin)
-            group("cin", sum(int(np.prod(shp)) for shp in shapes.values()), partial(cin_pack, shapes=shapes),
-                  partial(cin_unpack, shapes=shapes), ("adam/nm", "adam/nv"), reg=(sp.l2, sum(self.cin), self.opt[8:]))
-            self.cin_h = (_lib.C.c_int32 * 3)(*self.cin)
-            self.z_cin = z(B)
-        # AutoInt's interacting layers (ModelSpec.autoint_layers, csrc/autoint.hip): [w | Wq_1 | Wk_1 | Wv_1 |
-        # Wr_1 | Wq_2 ..] and the logit z_autoint [B] (the other branches' logits already added: the head's one
-        # z_extra); the backward recomputes in LDS and keeps nothing in HBM.  L2 on w = autoint_res, the output
-        # layer's AutoInt part, as on cin_res; nothing on the layer matrices
-        self.autoint = sp.autoint_layers
-        if self.autoint:
-            shapes = autoint_shapes(sp.afm_fields, sp.E, self.autoint, sp.autoint_dim)
-            group("autoint", sum(int(np.prod(shp)) for shp in shapes.values()), partial(autoint_pack, shapes=shapes),
-                  partial(autoint_unpack, shapes=shapes), ("adam/im", "adam/iv"),
-                  reg=(sp.l2, sp.afm_fields * sp.autoint_dim, self.opt[8:]))
-            self.z_autoint = z(B)
-        # product layer (ModelSpec.pnn, csrc/pnn.hip): theta [D1, F]; lp itself is added into h[0] and kept
-        # nowhere.  No regulariser (PNN.py:136-139 has none on it)
-        self.pnn = sp.pnn
-        if self.pnn:
-            D1, F = sp.hidden[0], sp.afm_fields
-            group("pnn", D1 * F, partial(pnn_pack, D1=D1, F=F), partial(pnn_unpack, D1=D1, F=F),
-                  ("adam/pm", "adam/pv"))
+        # the side options (branches.py), each under its descriptor's key: the enabled ones' dense parameter
+        # vectors with their Adam moments and the backward's per-block partial sums (param_groups.py), in the order
+        # of their Adam launches, and the logit chain: per member its labels and entry points, its own leading
+        # arguments, its forward's private state and its logit z_<key> [B], every logit with the earlier ones
+        # already added, so the last is the head's one z_extra
+        self.groups, self.chain = {}, []
+        for b in BRANCHES:
+            on = getattr(sp, b.name)
+            setattr(self, b.key, on)
+            if not on:
+                continue
+            if b.ckpt_keys:
+                n, pack, unpack = b.layout(sp)
+                reg = dict(reg=(sp.l2, b.reg(sp), self.opt[8:])) if b.reg else {}
+                self.groups[b.key] = ParamGroup(b.key, n, "dl_%s_grid" % b.key, B, dev, pack, unpack, b.ckpt_keys, **reg)
+            if b.lead:
+                self.chain.append(SimpleNamespace(
+                    fwd=(b.key + "_fwd", "dl_%s_fwd" % b.key), bwd=(b.key + "_bwd", "dl_%s_bwd" % b.key),
+                    lead=b.lead(sp), whole_x0=b.whole_x0, g=self.groups[b.key],
+                    state=(z(*b.state(sp, B)),) if b.state else (), z=z(B)))
+        # the options that read x0's deep columns (all on the tower input)
+        self.reads_x0 = any(getattr(sp, b.name) for b in BRANCHES if b.phrases)
         # batch normalisation (ModelSpec.batch_norm, csrc/bn.hip), per hidden layer: [gamma | beta] as a
         # group of its own (no regulariser), [running_mean | running_var], the step's [mu_hi | mu_lo |
         # invstd] and xhat [B, h_ld]; the statistics' partials and the merged backward sums are consumed at
         # once and shared by the layers
-        self.bn = sp.batch_norm
         self.bn_groups = []
         if self.bn:
             dp = [_ru(h, 16) for h in sp.hidden]
@@ -1010,56 +851,10 @@ class CTREngine:
         w[:-1] = rng.standard_normal(self.head_n - 1) * g
         w[-1] = rng.standard_normal()
         self.w_head[: self.head_n].copy_(torch.from_numpy(w))
-        if self.cross:
-            # DCN.py:75-79 cross_layer / cross_bias ~ N(0, sqrt(2 / (D + D))); :90-93 the output
-            # layer's cross part ~ N(0, sqrt(2 / (D + H + 1)))
-            D, Lc = self.D0, self.cross
-            v = rng.standard_normal((2 * Lc + 1, D)) * math.sqrt(2.0 / (D + D))
-            v[0] = rng.standard_normal(D) * math.sqrt(2.0 / (D + H + 1))
-            cross = self.groups["cross"]     # (v is drawn in the device vector's own column order)
-            cross.load(cross.unpack(v.astype(np.float32).reshape(-1)))
-        if self.afm:
-            # AFM.py:75-85: attention_w, attention_b ~ N(0, sqrt(2 / (A + E))); attention_h, attention_p ~ N(0, 1)
-            A, g = self.afm, math.sqrt(2.0 / (self.afm + sp.E))
-            P = {"attention_w": rng.standard_normal((sp.E, A)) * g, "attention_b": rng.standard_normal((1, A)) * g,
-                 "attention_h": rng.standard_normal((1, A)), "attention_p": rng.standard_normal((sp.E, 1))}
-            self.groups["afm"].load(P)
-        if self.ccpm:
-            # Keras' defaults (CCPM.py:56-68 passes no initializer): glorot_uniform kernels, zero biases
-            P = {}
-            for k, shp in ccpm_shapes(sp.ccpm_dims()).items():
-                if k.endswith(".bias"):
-                    P[k] = np.zeros(shp, np.float32)
-                else:
-                    rf = shp[0] * shp[1] if len(shp) == 4 else 1
-                    lim = math.sqrt(6.0 / (rf * (shp[-2] + shp[-1])))
-                    P[k] = rng.uniform(-lim, lim, shp)
-            self.groups["ccpm"].load(P)
-        if self.cin:
-            # cin_layer_* glorot-uniform (fan-in H_{k-1} F, fan-out H_k); cin_res ~ N(0, sqrt(2 / (sum H + 1))) as deep_res
-            P = {}
-            for k, shp in cin_shapes(sp.afm_fields, self.cin).items():
-                if k == "cin_res":
-                    P[k] = rng.standard_normal(shp) * math.sqrt(2.0 / (shp[0] + 1))
-                else:
-                    lim = math.sqrt(6.0 / (shp[0] + shp[1]))
-                    P[k] = rng.uniform(-lim, lim, shp)
-            self.groups["cin"].load(P)
-        if self.autoint:
-            # autoint_{q,k,v,r}_* glorot-uniform (fan-in D_{l-1}, fan-out D); autoint_res ~ N(0, sqrt(2 / (F D + 1)))
-            # as deep_res
-            P = {}
-            for k, shp in autoint_shapes(sp.afm_fields, sp.E, self.autoint, sp.autoint_dim).items():
-                if k == "autoint_res":
-                    P[k] = rng.standard_normal(shp) * math.sqrt(2.0 / (shp[0] + 1))
-                else:
-                    lim = math.sqrt(6.0 / (shp[0] + shp[1]))
-                    P[k] = rng.uniform(-lim, lim, shp)
-            self.groups["autoint"].load(P)
-        if self.pnn:
-            # PNN.py:57: product-quadratic-inner ~ N(0, 0.01)
-            v = rng.standard_normal((sp.hidden[0], sp.afm_fields)) * 0.01
-            self.groups["pnn"].load({PNN_KEY: v})
+        for b in BRANCHES:      # in the order of the table: rng is consumed branch by branch
+            g = self.groups.get(b.key)
+            if g is not None:
+                g.load(b.init(rng, sp, g.unpack))
         if self.wide_lazy:
             self._wide_pack()
         torch.cuda.synchronize()
@@ -1425,7 +1220,7 @@ class CTREngine:
         sp = self.spec
         if os.environ.get("DLAMD_FUSED_GATHER", "1") == "0" or not self.s3 or self.bf or sp.M:
             return False
-        if self.cross or self.afm or self.pnn or self.bi or self.ccpm or self.cin or self.autoint:   # all read x0's deep columns, which the fused forms leave unwritten
+        if self.reads_x0:   # the fused forms leave x0's deep columns unwritten
             return False
         if self.bn:   # the fused forms apply the ReLU themselves; layer 0 must store its pre-activation
             return False
@@ -1788,31 +1583,16 @@ class CTREngine:
                     self.head_blocks, sp.F, self._keep_thr(k1), self._keep_inv(k1), self._keep_thr(k2),
                     self._keep_inv(k2), self.seed & 0xFFFFFFFFFFFFFFFF, ptr(self.opt), ptr(self.fm_keep), s)
             return
-        if self.cross or self.afm or self.ccpm or self.cin or self.autoint:
-            # x0 is complete here (in lazy training the first layer's fused row gather wrote its
-            # deep columns): s and z_cross, z_afm (+ z_cross), z_ccpm (+ those), z_cin (+ those), z_autoint
-            # (+ those), then the head with that extra logit
-            if self.cross:
-                self._c("cross_fwd", "dl_cross_fwd", B, self.D0, self.cross, ptr(self.x0), self.in_ld[0],
-                        ptr(self.groups["cross"].w), ptr(self.cross_s), ptr(self.z_cross), s)
-            if self.afm:
-                self._c("afm_fwd", "dl_afm_fwd", B, sp.afm_fields, sp.E, self.afm, ptr(self.x0), self.in_ld[0],
-                        self.cat_col, ptr(self.groups["afm"].w), ptr(self.z_cross) if self.cross else None,
-                        ptr(self.afm_stats), ptr(self.z_afm), s)
-            z_extra = self.z_afm if self.afm else self.z_cross if self.cross else None
-            if self.ccpm:
-                self._c("ccpm_fwd", "dl_ccpm_fwd", B, sp.afm_fields, sp.E, len(self.ccpm), self.ccpm_f, ptr(self.x0),
-                        self.in_ld[0], self.cat_col, ptr(self.groups["ccpm"].w), ptr(z_extra), ptr(self.z_ccpm), s)
-                z_extra = self.z_ccpm
-            if self.cin:
-                self._c("cin_fwd", "dl_cin_fwd", B, sp.afm_fields, sp.E, len(self.cin), self.cin_h, ptr(self.x0),
-                        self.in_ld[0], self.cat_col, ptr(self.groups["cin"].w), ptr(z_extra), ptr(self.z_cin), s)
-                z_extra = self.z_cin
-            if self.autoint:
-                self._c("autoint_fwd", "dl_autoint_fwd", B, sp.afm_fields, sp.E, self.autoint, sp.autoint_heads,
-                        sp.autoint_dim, ptr(self.x0), self.in_ld[0], self.cat_col, ptr(self.groups["autoint"].w),
-                        ptr(z_extra), ptr(self.z_autoint), s)
-                z_extra = self.z_autoint
+        if self.chain:
+            # x0 is complete here (in lazy training the first layer's fused row gather wrote its deep columns):
+            # every member's logit with the one before it added (z_in; NULL for the first), then the head with
+            # the last as its extra logit
+            z_extra = None
+            for c in self.chain:
+                x0 = (ptr(self.x0), self.in_ld[0]) if c.whole_x0 else (ptr(self.x0), self.in_ld[0], self.cat_col)
+                z_in = () if c.whole_x0 else (ptr(z_extra),)
+                self._c(*c.fwd, B, *c.lead, *x0, ptr(c.g.w), *z_in, *map(ptr, c.state), ptr(c.z), s)
+                z_extra = c.z
             self._c("head", "dl_head_fwd_bwd_cross" + sw, B, sp.fm_cols, H, ptr(self.fm_out), self.fm_ld,
                     ptr(self.h[-1]), self.h_ld[-1], ptr(self.w_head), ptr(self.in_label), sp.logloss_eps, *scale,
                     ptr(z_extra), ptr(self.score), ptr(self.z), ptr(self.dz),
@@ -1908,37 +1688,13 @@ class CTREngine:
                                         _num_splits(B, dws[l], 64), self.in_ld[l], self.out_ld[l], l1, l2, 0)
             self._adam_lay = lay   # kept alive: a captured graph's kernel arguments were copied at launch
             self._c("adam_dense", "dl_adam_dense_layers", nl, C_ref(lay), 3 if self.s3 else 1, ptr(self.opt), s)
-        if self.cross:
-            # gemm_dx_l0 has written dx0 (the embedding columns of x0, from column cat_col); the cross
-            # network's share is added before the embedding backward reads it
-            g = self.groups["cross"]
-            self._c("cross_bwd", "dl_cross_bwd", B, self.D0, self.cross, ptr(self.x0), self.in_ld[0], ptr(g.w),
-                    ptr(self.cross_s), ptr(self.dz), ptr(self.dx0), self.dx_ld, self.cat_col, self.dx_cols,
-                    ptr(g.slab), g.blocks, s)
-        if self.afm:
-            # the attentional interactions' share of dx0's field columns, likewise before the embedding backward
-            g = self.groups["afm"]
-            self._c("afm_bwd", "dl_afm_bwd", B, sp.afm_fields, sp.E, self.afm, ptr(self.x0), self.in_ld[0],
-                    self.cat_col, ptr(g.w), ptr(self.afm_stats), ptr(self.dz), ptr(self.dx0), self.dx_ld, 0,
-                    ptr(g.slab), g.blocks, s)
-        if self.ccpm:
-            # the CCPM branch's share of dx0's field columns, likewise
-            g = self.groups["ccpm"]
-            self._c("ccpm_bwd", "dl_ccpm_bwd", B, sp.afm_fields, sp.E, len(self.ccpm), self.ccpm_f, ptr(self.x0),
-                    self.in_ld[0], self.cat_col, ptr(g.w), ptr(self.dz), ptr(self.dx0), self.dx_ld, 0,
-                    ptr(g.slab), g.blocks, s)
-        if self.cin:
-            # the compressed interaction network's share of dx0's field columns, likewise
-            g = self.groups["cin"]
-            self._c("cin_bwd", "dl_cin_bwd", B, sp.afm_fields, sp.E, len(self.cin), self.cin_h, ptr(self.x0),
-                    self.in_ld[0], self.cat_col, ptr(g.w), ptr(self.dz), ptr(self.dx0), self.dx_ld, 0,
-                    ptr(g.slab), g.blocks, s)
-        if self.autoint:
-            # the interacting layers' share of dx0's field columns, likewise
-            g = self.groups["autoint"]
-            self._c("autoint_bwd", "dl_autoint_bwd", B, sp.afm_fields, sp.E, self.autoint, sp.autoint_heads,
-                    sp.autoint_dim, ptr(self.x0), self.in_ld[0], self.cat_col, ptr(g.w), ptr(self.dz), ptr(self.dx0),
-                    self.dx_ld, 0, ptr(g.slab), g.blocks, s)
+        for c in self.chain:
+            # gemm_dx_l0 has written dx0 (the embedding columns of x0, from column cat_col); every chain member's
+            # share is added before the embedding backward reads it (the cross network's over its own window)
+            x0 = (ptr(self.x0), self.in_ld[0]) if c.whole_x0 else (ptr(self.x0), self.in_ld[0], self.cat_col)
+            window = (self.cat_col, self.dx_cols) if c.whole_x0 else (0,)
+            self._c(*c.bwd, B, *c.lead, *x0, ptr(c.g.w), *map(ptr, c.state), ptr(self.dz), ptr(self.dx0), self.dx_ld,
+                    *window, ptr(c.g.slab), c.g.blocks, s)
         if self.pnn:
             # the product layer's share, from the ReluGrad-masked dh[0] the tower's backward formed
             g = self.groups["pnn"]

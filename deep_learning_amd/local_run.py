@@ -51,6 +51,7 @@ gauc_slot=K, the cate_feats column whose id groups the samples for GAUC (the use
 import sys
 import time
 
+from .branches import BRANCHES, KEYWORDS, SIDE_MODELS
 from .utils import data_loader as data_load
 from .utils import my_utils
 
@@ -84,6 +85,7 @@ class ModelParams:
         self.batch_size = 1024
         self.shuffle = 1
         self.shuffle_seed = None
+        spelt = {}      # the side options as given, for their refusals
         for kv in argv[14:]:
             k, v = kv.split("=", 1)
             if k == "hidden_units":
@@ -104,22 +106,9 @@ class ModelParams:
                 if not v:
                     raise SystemExit("weight_key= needs the name of a float [1] TFRecord feature")
                 self.weight_key = v
-            elif k == "cross_layers":   # a cross network beside the dnn_* tower, stored only when given
-                self.cross_layers = check_cross_layers(v, self.alg_name)
-            elif k == "afm_attention":   # attentional pairwise interactions beside the tower, likewise
-                self.afm_attention = check_afm_attention(v, self.alg_name)
-            elif k == "pnn":             # the product layer in front of the tower, likewise
-                self.pnn = check_pnn(v, self.alg_name)
-            elif k in ("batch_norm", "bn_eps", "bn_momentum"):   # batch normalisation in the tower, likewise
-                setattr(self, k, check_batch_norm(k, v))
-            elif k == "bi_interaction":   # the Bi-Interaction pooling into the tower input, likewise
-                self.bi_interaction = check_bi_interaction(v, self.alg_name)
-            elif k == "ccpm_filters":     # the CCPM branch beside the tower, likewise
-                self.ccpm_filters = check_ccpm_filters(v, self.alg_name)
-            elif k == "cin_layers":       # the compressed interaction network beside the tower, likewise
-                self.cin_layers = check_cin_layers(v, self.alg_name)
-            elif k in ("autoint_layers", "autoint_heads", "autoint_dim"):   # AutoInt's interacting layers, likewise
-                setattr(self, k, check_autoint_option(k, v, self.alg_name))
+            elif k in KEYWORDS:   # a side option of the tower (branches.py), stored only when given as well
+                setattr(self, k, parse_side_option(KEYWORDS[k], k, v, self.alg_name))
+                spelt[k] = kv
             elif k in ("wide_optimizer", "wide_lr", "wide_l1", "wide_l2"):   # stored only when given, too
                 setattr(self, k, check_wide_option(k, v, self.alg_name))
             else:
@@ -127,13 +116,7 @@ class ModelParams:
         (self.cont_field_size, self.vector_feats_size, self.cate_field_size, self.multi_feats_size,
          self.multi_field_size, self.multi_feats_range) = my_utils.feat_size(self.feat_conf_path, self.alg_name)
         check_eval_options(getattr(self, "eval_metrics", None), getattr(self, "gauc_slot", None), self.cate_field_size)
-        if hasattr(self, "ccpm_filters"):   # the map's limits, known now that the fields are counted
-            check_ccpm_map(self.ccpm_filters, self.embedding_size, self.cate_field_size + self.multi_field_size)
-        if hasattr(self, "cin_layers"):     # likewise
-            check_cin_fields(self.cin_layers, self.embedding_size, self.cate_field_size + self.multi_field_size)
-        if getattr(self, "autoint_layers", 0):   # likewise; 0 is off, whatever the other two say
-            check_autoint_shape(self.autoint_layers, getattr(self, "autoint_heads", 2), getattr(self, "autoint_dim", 16),
-                                self.embedding_size, self.cate_field_size + self.multi_field_size)
+        check_side_options(self, spelt)      # the fields' limits, known now that they are counted
 
 
 EVAL_METRICS = ("auc", "gauc", "logloss", "calibration")
@@ -150,160 +133,32 @@ def check_pos_weight(v):
     return w
 
 
-def check_cross_layers(v, alg_name):
-    """cross_layers=N as an int; refuses (SystemExit) anything but an integer >= 0, and N > 0 for a
-    model other than the dnn_* ones or beyond what the engine takes."""
-    from .engine import ModelSpec
-    try:
-        n = int(v)
-    except ValueError:
-        raise SystemExit("cross_layers=%s is not an integer" % v)
-    if n < 0 or n > ModelSpec.CROSS_MAX_LAYERS:
-        raise SystemExit("cross_layers=%s must lie in [0, %d]" % (v, ModelSpec.CROSS_MAX_LAYERS))
-    if n and alg_name not in ModelSpec.CROSS_MODELS:
-        raise SystemExit("cross_layers=%s: the cross network joins the tower of %s only, not %s"
-                         % (v, ", ".join(ModelSpec.CROSS_MODELS), alg_name))
-    return n
+def parse_side_option(b, k, v, alg_name):
+    """Keyword k=v of the side option b (a branches.py descriptor) as its value; refuses (SystemExit) what the
+    text alone shows: a value its parser does not take, and switching the option on for a model other than
+    the dnn_* ones.  (What depends on the fields is refused once they are counted: check_side_options.)"""
+    value = b.parse(k, v)
+    if k == b.name and value and b.phrases and alg_name not in SIDE_MODELS:
+        raise SystemExit("%s=%s: %s the tower of %s only, not %s"
+                         % (k, v, b.phrases[0], ", ".join(SIDE_MODELS), alg_name))
+    return value
 
 
-def check_afm_attention(v, alg_name):
-    """afm_attention=A as an int; refuses (SystemExit) anything but an integer in [0, AFM_MAX_ATT],
-    and A > 0 for a model other than the dnn_* ones."""
-    from .engine import ModelSpec
-    try:
-        n = int(v)
-    except ValueError:
-        raise SystemExit("afm_attention=%s is not an integer" % v)
-    if n < 0 or n > ModelSpec.AFM_MAX_ATT:
-        raise SystemExit("afm_attention=%s must lie in [0, %d]" % (v, ModelSpec.AFM_MAX_ATT))
-    if n and alg_name not in ModelSpec.CROSS_MODELS:
-        raise SystemExit("afm_attention=%s: the attentional interactions join the tower of %s only, not %s"
-                         % (v, ", ".join(ModelSpec.CROSS_MODELS), alg_name))
-    return n
-
-
-def check_pnn(v, alg_name):
-    """pnn=inner as a string; refuses (SystemExit) any other value, and a model other than the dnn_* ones."""
-    from .engine import ModelSpec
-    if v == "outer":
-        raise SystemExit("pnn=outer: the outer-product layer is not built; pnn=inner is")
-    if v != "inner":
-        raise SystemExit("pnn=%s must be inner" % v)
-    if alg_name not in ModelSpec.CROSS_MODELS:
-        raise SystemExit("pnn=%s: the product layer feeds the tower of %s only, not %s"
-                         % (v, ", ".join(ModelSpec.CROSS_MODELS), alg_name))
-    return v
-
-
-def check_bi_interaction(v, alg_name):
-    """bi_interaction=0|1 as a bool; refuses (SystemExit) any other value, and bi_interaction=1 for a
-    model other than the dnn_* ones."""
-    from .engine import ModelSpec
-    if v not in ("0", "1"):
-        raise SystemExit("bi_interaction=%s must be 0 or 1" % v)
-    if v == "1" and alg_name not in ModelSpec.CROSS_MODELS:
-        raise SystemExit("bi_interaction=%s: the Bi-Interaction pooling feeds the tower of %s only, not %s"
-                         % (v, ", ".join(ModelSpec.CROSS_MODELS), alg_name))
-    return v == "1"
-
-
-def check_ccpm_filters(v, alg_name):
-    """ccpm_filters=C0,C1,.. as a list of ints; refuses (SystemExit) anything but 1 to CCPM_MAX_LAYERS
-    integers in [1, CCPM_MAX_FILTERS], and a model other than the dnn_* ones.  (The field count and the
-    embedding size are known only once the model is built: ModelSpec refuses those.)"""
-    from .engine import ModelSpec
-    try:
-        f = [int(x) for x in v.split(",")]
-    except ValueError:
-        raise SystemExit("ccpm_filters=%s is not a comma-separated list of integers" % v)
-    if not 1 <= len(f) <= ModelSpec.CCPM_MAX_LAYERS or not all(1 <= c <= ModelSpec.CCPM_MAX_FILTERS for c in f):
-        raise SystemExit("ccpm_filters=%s must hold 1 to %d values in [1, %d]"
-                         % (v, ModelSpec.CCPM_MAX_LAYERS, ModelSpec.CCPM_MAX_FILTERS))
-    if alg_name not in ModelSpec.CROSS_MODELS:
-        raise SystemExit("ccpm_filters=%s: the convolutional interactions join the tower of %s only, not %s"
-                         % (v, ", ".join(ModelSpec.CROSS_MODELS), alg_name))
-    return f
-
-
-def check_ccpm_map(filters, E, F):
-    """Refuses (SystemExit) an [E, F] field map the CCPM branch does not take: what ModelSpec would."""
-    from .engine import ModelSpec
-    Lc = len(filters)
-    if E not in ModelSpec.CCPM_EMB or not 2 <= F <= ModelSpec.CCPM_MAX_FIELDS or (F >> Lc) < 1 or (E >> Lc) < 1:
-        raise SystemExit("ccpm_filters=%s: 2 to %d embedded fields of size %s, every layer halving the map to at "
-                         "least 1 x 1; got %d fields of size %d"
-                         % (",".join(map(str, filters)), ModelSpec.CCPM_MAX_FIELDS,
-                            " / ".join(map(str, ModelSpec.CCPM_EMB)), F, E))
-
-
-def check_cin_layers(v, alg_name):
-    """cin_layers=H1,H2,.. as a list of ints; refuses (SystemExit) anything but 1 to CIN_MAX_LAYERS integers
-    in [1, CIN_MAX_MAPS], and a model other than the dnn_* ones.  (The field count and the embedding size
-    are known only once the fields are counted: check_cin_fields refuses those.)"""
-    from .engine import ModelSpec
-    try:
-        h = [int(x) for x in v.split(",")]
-    except ValueError:
-        raise SystemExit("cin_layers=%s is not a comma-separated list of integers" % v)
-    if not 1 <= len(h) <= ModelSpec.CIN_MAX_LAYERS or not all(1 <= x <= ModelSpec.CIN_MAX_MAPS for x in h):
-        raise SystemExit("cin_layers=%s must hold 1 to %d values in [1, %d]"
-                         % (v, ModelSpec.CIN_MAX_LAYERS, ModelSpec.CIN_MAX_MAPS))
-    if alg_name not in ModelSpec.CROSS_MODELS:
-        raise SystemExit("cin_layers=%s: the compressed interaction network joins the tower of %s only, not %s"
-                         % (v, ", ".join(ModelSpec.CROSS_MODELS), alg_name))
-    return h
-
-
-def check_cin_fields(layers, E, F):
-    """Refuses (SystemExit) the F fields of size E the CIN does not take: what ModelSpec would."""
-    from .engine import ModelSpec
-    H = [F] + list(layers)
-    nw = sum(H[k + 1] * H[k] * F for k in range(len(layers)))
-    if E not in ModelSpec.CIN_EMB or not 2 <= F <= ModelSpec.CIN_MAX_FIELDS or nw > ModelSpec.CIN_MAX_WEIGHTS:
-        raise SystemExit("cin_layers=%s: 2 to %d embedded fields of size %s and at most %d layer weights; got %d "
-                         "fields of size %d (%d weights)"
-                         % (",".join(map(str, layers)), ModelSpec.CIN_MAX_FIELDS,
-                            " / ".join(map(str, ModelSpec.CIN_EMB)), ModelSpec.CIN_MAX_WEIGHTS, F, E, nw))
-
-
-def check_autoint_option(k, v, alg_name):
-    """autoint_layers=L, autoint_heads=Hn or autoint_dim=D as an int; refuses (SystemExit) anything but an
-    integer, and autoint_layers != 0 on a model other than the dnn_* ones.  (The accepted shapes depend on all
-    three and on the fields: check_autoint_shape refuses those once the fields are counted.)"""
-    from .engine import ModelSpec
-    try:
-        n = int(v)
-    except ValueError:
-        raise SystemExit("autoint_layers: %s=%s is not an integer" % (k, v))
-    if k == "autoint_layers" and n and alg_name not in ModelSpec.CROSS_MODELS:
-        raise SystemExit("autoint_layers=%s: the interacting layers join the tower of %s only, not %s"
-                         % (v, ", ".join(ModelSpec.CROSS_MODELS), alg_name))
-    return n
-
-
-def check_autoint_shape(L, Hn, D, E, F):
-    """Refuses (SystemExit) the layers, heads, columns and fields the interacting layers do not take: what
-    ModelSpec would."""
-    from .engine import autoint_refusal
-    why = autoint_refusal(L, Hn, D, F, E)
-    if why:
-        raise SystemExit(why)
-
-
-def check_batch_norm(k, v):
-    """batch_norm=0|1 as a bool, bn_eps / bn_momentum as floats; refuses (SystemExit) what ModelSpec
-    would: bn_eps <= 0, bn_momentum outside (0, 1], anything not finite."""
-    if k == "batch_norm":
-        if v not in ("0", "1"):
-            raise SystemExit("batch_norm=%s must be 0 or 1" % v)
-        return v == "1"
-    try:
-        x = float(v)
-    except ValueError:
-        raise SystemExit("%s=%s is not a number" % (k, v))
-    if not (0.0 < x < float("inf")) or (k == "bn_momentum" and x > 1.0):
-        raise SystemExit("%s=%s must %s" % (k, v, "lie in (0, 1]" if k == "bn_momentum" else "be finite and > 0"))
-    return x
+def check_side_options(mp, spelt):
+    """Refuses (SystemExit) every side option that is on in the ModelParams mp and whose kernels do not take its
+    fields, counted by now: the descriptor's refusal, which ModelSpec raises as a ValueError.  An option of one
+    keyword is named as it was spelt (spelt: {keyword: "keyword=text"}), one of several by its name."""
+    from .engine import FAMILIES
+    E, F = mp.embedding_size, mp.cate_field_size + mp.multi_field_size
+    for b in BRANCHES:
+        values = b.values(mp)
+        if not (values[0] and b.refusal):
+            continue
+        deep_in = (F * E + (mp.cont_field_size if FAMILIES[mp.alg_name]["cont"] else 0) + mp.vector_feats_size
+                   + (E if getattr(mp, "bi_interaction", False) else 0))      # ModelSpec.deep_in
+        why = b.refusal(F, E, deep_in, *values)
+        if why:
+            raise SystemExit("%s: %s" % (spelt[b.name] if len(b.keywords) == 1 else b.name, why))
 
 
 def check_wide_option(k, v, alg_name):

@@ -31,6 +31,7 @@ import torch
 
 import inspect
 
+from ..branches import KEYWORDS
 from ..engine import FAMILIES, CTREngine, ModelSpec, default_adam
 from ..metrics import AucAccumulator, EvalAccumulator
 
@@ -52,24 +53,9 @@ def _spec_from_args(model, args):
         kw.update(dropout_keep_fm=[float(k) for k in keep_fm])
     if getattr(args, "pos_weight", None) is not None:   # local_run's pos_weight= (stored only when given)
         kw.update(pos_weight=float(args.pos_weight))
-    if getattr(args, "cross_layers", None) is not None:   # local_run's cross_layers= (stored only when given)
-        kw.update(cross_layers=int(args.cross_layers))
-    if getattr(args, "afm_attention", None) is not None:   # local_run's afm_attention= (stored only when given)
-        kw.update(afm_attention=int(args.afm_attention))
-    if getattr(args, "pnn", None) is not None:             # local_run's pnn= (stored only when given)
-        kw.update(pnn=args.pnn)
-    for k in ("batch_norm", "bn_eps", "bn_momentum"):      # local_run's batch_norm= bn_eps= bn_momentum=, likewise
+    for k in KEYWORDS:     # local_run's side options (stored only when given); ModelSpec coerces them
         if getattr(args, k, None) is not None:
             kw[k] = getattr(args, k)
-    if getattr(args, "bi_interaction", None) is not None:  # local_run's bi_interaction= (stored only when given)
-        kw.update(bi_interaction=bool(args.bi_interaction))
-    if getattr(args, "ccpm_filters", None) is not None:    # local_run's ccpm_filters= (stored only when given)
-        kw.update(ccpm_filters=tuple(int(c) for c in args.ccpm_filters))
-    if getattr(args, "cin_layers", None) is not None:      # local_run's cin_layers= (stored only when given)
-        kw.update(cin_layers=tuple(int(h) for h in args.cin_layers))
-    for k in ("autoint_layers", "autoint_heads", "autoint_dim"):   # local_run's autoint_*= (stored only when given)
-        if getattr(args, k, None) is not None:
-            kw[k] = int(getattr(args, k))
     return ModelSpec(model, **kw)
 
 

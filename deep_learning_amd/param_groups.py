@@ -6,6 +6,8 @@ partial gradient sums [dl_<x>_grid(max_batch), n] its backward kernel fills, and
 launch per step.  The layouts are pure host functions (numpy in, numpy out) between the reference's keys
 and shapes and the device vector; ParamGroup holds the buffers and does the rest.
 """
+from functools import partial
+
 import numpy as np
 import torch
 
@@ -18,8 +20,8 @@ def _ru(x, m):
 
 
 def _shapes_pack(P, shapes, what=""):
-    """{key: shape} in the device vector's order -> the concatenated vector; a variable of another size
-    is refused."""
+    """Reference-layout parameters P and {key: shape} in the device vector's order -> the concatenated
+    vector; a variable of another size is refused, the message opening with `what` (the option's name)."""
     parts = []
     for k, shp in shapes.items():
         a = np.asarray(P[k], np.float32)
@@ -72,16 +74,6 @@ def afm_shapes(E, A):
     return {"attention_p": (E, 1), "attention_h": (1, A), "attention_b": (1, A), "attention_w": (E, A)}
 
 
-def afm_pack(P, E, A):
-    """Reference-layout attention parameters -> the device vector [p | h | b | W]."""
-    return _shapes_pack(P, afm_shapes(E, A))
-
-
-def afm_unpack(v, E, A):
-    """Inverse of afm_pack: {key: numpy in the reference's shape}."""
-    return _shapes_unpack(v, afm_shapes(E, A))
-
-
 def ccpm_shapes(dims):
     """ModelSpec.ccpm_dims() -> {variable: Keras shape} in the device vector's order: ccpm_out.kernel
     [H_L W_L C_L, 1], then per layer ccpm_conv_{l}.kernel [3, 3, C_{l-1}, C_l] and ccpm_conv_{l}.bias [C_l]."""
@@ -92,17 +84,6 @@ def ccpm_shapes(dims):
     return out
 
 
-def ccpm_pack(P, shapes):
-    """Reference-layout CCPM parameters -> the device vector [p | K_0 | b_0 | ..]; a variable of another
-    size is refused."""
-    return _shapes_pack(P, shapes, "ccpm_filters: ")
-
-
-def ccpm_unpack(v, shapes):
-    """Inverse of ccpm_pack: {key: numpy in the reference's shape}."""
-    return _shapes_unpack(v, shapes)
-
-
 def cin_shapes(F, layers):
     """The CIN variables in the device vector's order [c | W^1 | W^2 ..]: cin_res [sum H_k, 1], then per
     layer cin_layer_{k-1} [H_{k-1} F, H_k] (row i F + j; H_0 = F)."""
@@ -111,17 +92,6 @@ def cin_shapes(F, layers):
     for k in range(len(layers)):
         out["cin_layer_%d" % k] = (H[k] * F, H[k + 1])
     return out
-
-
-def cin_pack(P, shapes):
-    """Reference-layout CIN parameters -> the device vector [c | W^1 | ..]; a variable of another size is
-    refused."""
-    return _shapes_pack(P, shapes, "cin_layers: ")
-
-
-def cin_unpack(v, shapes):
-    """Inverse of cin_pack: {key: numpy in the reference's shape}."""
-    return _shapes_unpack(v, shapes)
 
 
 def autoint_shapes(F, E, L, D):
@@ -135,15 +105,19 @@ def autoint_shapes(F, E, L, D):
     return out
 
 
-def autoint_pack(P, shapes):
-    """Reference-layout AutoInt parameters -> the device vector [w | Wq_1 | ..]; a variable of another size
-    is refused."""
-    return _shapes_pack(P, shapes, "autoint_layers: ")
+# the pack / unpack names of the shapes layouts, for callers outside the package: _shapes_pack with the
+# option's name as the refusal's prefix, and its inverse
+ccpm_pack, cin_pack, autoint_pack = (partial(_shapes_pack, what=w + ": ")
+                                     for w in ("ccpm_filters", "cin_layers", "autoint_layers"))
+ccpm_unpack = cin_unpack = autoint_unpack = _shapes_unpack
 
 
-def autoint_unpack(v, shapes):
-    """Inverse of autoint_pack: {key: numpy in the reference's shape}."""
-    return _shapes_unpack(v, shapes)
+def afm_pack(P, E, A):
+    return _shapes_pack(P, afm_shapes(E, A))
+
+
+def afm_unpack(v, E, A):
+    return _shapes_unpack(v, afm_shapes(E, A))
 
 
 PNN_KEY = "product-quadratic-inner"   # PNN.py:57, [D1, F]: the device vector is its row-major image

@@ -50,6 +50,7 @@ import torch.distributed as dist
 
 from . import _lib
 from ._lib import call, ptr
+from .branches import unsupported
 from .engine import CTREngine, C_ref, _num_splits, _ru, call_int, capture_guard
 
 _STICKY = _lib.STATUS_LAG | _lib.STATUS_INDEX | _lib.STATUS_OVERFLOW | _lib.STATUS_DESYNC
@@ -179,19 +180,7 @@ class ShardedCTREngine(CTREngine):
         if spec.dropout_keep_fm:
             raise ValueError("dropout_keep_fm: not supported by ShardedCTREngine (the mask is indexed by the "
                              "local row number; a sharded batch needs global rows)")
-        flat = "gradients are not part of the flat all-reduce"
-        for opt, on, why in (
-                ("cross_layers", spec.cross_layers, "the cross parameters' " + flat),
-                ("afm_attention", spec.afm_attention, "the attention parameters' " + flat),
-                ("pnn", spec.pnn, "theta's gradient is not part of the flat all-reduce"),
-                ("ccpm_filters", spec.ccpm_filters, "the convolution parameters' " + flat),
-                ("cin_layers", spec.cin_layers, "the interaction network's parameters' " + flat),
-                ("autoint_layers", spec.autoint_layers, "the interacting layers' parameters' " + flat),
-                ("bi_interaction", spec.bi_interaction, "its step does not launch the pooling's kernels around the "
-                                                        "first tower layer"),
-                ("batch_norm", spec.batch_norm, "the batch statistics would need a reduction across the ranks")):
-            if on:
-                raise ValueError("%s: not supported by ShardedCTREngine (%s)" % (opt, why))
+        unsupported(spec, "ShardedCTREngine")      # every side option (branches.py), with its reason
         # the status ring holds 4 reports (slot k & 3) and the host reads report k only after
         # k + lag was submitted: lag <= 3, or report k + 4 overwrites k before it is read
         if not 0 <= int(lag) <= 3:

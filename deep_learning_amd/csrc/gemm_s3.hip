@@ -174,11 +174,42 @@ __device__ __forceinline__ void nt_rd3(uint32_t a, shortx8& h, shortx8& m, short
 // s_waitcnt vmcnt(n) (n < 64), other counters untouched
 #define DL_WAIT_VMCNT(n) __builtin_amdgcn_s_waitcnt(((n) & 0xF) | (((n) >> 4) << 14) | (0x7 << 4) | (0xF << 8))
 
+// DL_S3_ROLLED (1; -DDL_S3_ROLLED=0 builds the A/B arm): the register epilogue rolled into the
+// last k chunk (below) instead of run after it.
+#ifndef DL_S3_ROLLED
+#define DL_S3_ROLLED 1
+#endif
+
+// OR of a value over the four lanes L, L ^ 16, L ^ 32, L ^ 48.  VALU is gfx950's row swaps
+// (v_permlane16_swap: odd rows of the first operand <-> even rows of the second; v_permlane32_swap:
+// rows 2, 3 <-> rows 0, 1), for use between MFMAs whose weight reads are counted by hand in lgkmcnt:
+// a ds_bpermute there makes the compiler wait for lgkmcnt(0), the prefetched fragments included.
+template <bool VALU>
+__device__ __forceinline__ uint32_t or_rows4(uint32_t v) {
+  if constexpr (VALU) {
+    const auto a = __builtin_amdgcn_permlane16_swap(v, v, false, false);
+    v = a[0] | a[1];
+    const auto b = __builtin_amdgcn_permlane32_swap(v, v, false, false);
+    return b[0] | b[1];
+  } else {
+    v |= (uint32_t)__shfl_xor((int)v, 16, 64);
+    v |= (uint32_t)__shfl_xor((int)v, 32, 64);
+    return v;
+  }
+}
+
 // DIRECT: the transposed accumulator layout (mfma_s3_t) and the epilogue straight from registers
 // — one 16-B store of four consecutive columns per lane and fragment (a wave instruction writes
 // 16 rows x 64 B), ReLU / ReluGrad bitmask in registers — instead of the transpose through the
-// LDS ring; the bitmask words the dX epilogue needs are loaded before the last k step.  Needs
-// N % 4 == 0, ldc % 4 == 0 and an even ldbits (the host picks it then; otherwise the LDS form).
+// LDS ring.  Needs N % 4 == 0, ldc % 4 == 0 and an even ldbits (the host picks it then; otherwise
+// the LDS form).  Without DROP the epilogue is rolled into the last k chunk: that chunk is a copy
+// of the step of its own (no prefetch, no barrier: nothing follows it), and once fragment f's
+// twelve MFMAs are issued, fragment f - 1 — final in its accumulators — is masked and stored,
+// before fragment f + 1's MFMAs; fragment 12 follows the chunk.  A wave's 1.7 MB / 8 of output
+// thus leaves under its own last 150 MFMAs instead of in a burst of all waves of all blocks
+// after them.  Same accumulators, masks, addresses and values as the epilogue after the loop
+// (which DROP keeps: its Philox draws would not fit the step's registers); the bitmask words the
+// dX epilogue needs are loaded before the last chunk either way.
 // GATHER: the embedding-lookup fusion of the flushed-table forward (dl_gemm_s3_nt_gather): the
 // first 32 g_chunks columns of A are fetched row by row from the table through the ids (an 8-float
 // piece never straddles two rows: E % 8 == 0), the rest from A as usual.  The values are the
@@ -312,16 +343,65 @@ __global__ __launch_bounds__(512) void gemm_s3_nt_kernel(S3Params p) {
   // loaded before the last k chunk's step (load_mw below), so the epilogue does not wait a
   // memory round trip for them and their 14 registers are not held through the main loop
   // (loaded before it they cost 7 spilled VGPRs)
+  // (the rolled form derives the epilogue's rows and columns from e_lane, made opaque where the
+  // main loop ends: computed there, the offsets and predicates do not live through the loop)
+  int e_lane = lane;
   uint32_t mw[DIRECT && EPI == S3_MASKBITS ? 2 : 1][7];
   auto load_mw = [&]() {
     if constexpr (DIRECT && EPI == S3_MASKBITS) {
 #pragma unroll
       for (int a = 0; a < 2; ++a) {
-        const int row = min(r0 + 16 * a + cl, p.M - 1);
+        const int row = min(r0 + 16 * a + (e_lane & 15), p.M - 1);
         const uint32_t* wp = reinterpret_cast<const uint32_t*>(p.bits + (long long)row * p.ldbits) + (j0 >> 5);
 #pragma unroll
         for (int i = 0; i < 7; ++i) mw[a][i] = wp[i];
       }
+    }
+  };
+
+  // The register epilogue of row fragment a, column fragment f (DIRECT).  Lane (kq, cl):
+  // acc[a][f][j] = C[r0 + 16a + cl][j0 + 16f + 4kq + j].  Stores go through a buffer descriptor:
+  // a piece past M or N gets an offset past its range and is dropped.
+  // (the training gather's plain-store form spills 16 B when rolled: it keeps the epilogue after the loop)
+  constexpr bool ROLL = DIRECT && !DROP && !(STORE_A && EPI == S3_STORE) && DL_S3_ROLLED;
+  const auto c_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.C, (short)0, DIRECT ? p.M * p.ldc * 4 : 0, 0x00020000);
+  [[maybe_unused]] uint32_t d_step = 0;
+  [[maybe_unused]] uint2 d_key = make_uint2(0u, 0u);
+  auto epi_frag = [&](int a, int f) {
+    const int cl = e_lane & 15, kq = e_lane >> 4;
+    const int row = r0 + 16 * a + cl;
+    const int col = j0 + 16 * f + 4 * kq;
+    floatx4 v = acc[a][f];
+    if (EPI == S3_RELU) {
+      v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f);
+    }
+    [[maybe_unused]] uint32_t kb = 0xFu;
+    if constexpr (DROP && EPI == S3_RELU) {   // the lane's four columns are one Philox group
+      kb = drop_keep4((uint32_t)row, (uint32_t)col >> 2, p.drop_layer, d_step, d_key, p.drop_thr);
+      v[0] = (kb & 1u) ? v[0] * p.drop_inv : 0.f; v[1] = (kb & 2u) ? v[1] * p.drop_inv : 0.f;
+      v[2] = (kb & 4u) ? v[2] * p.drop_inv : 0.f; v[3] = (kb & 8u) ? v[3] * p.drop_inv : 0.f;
+    }
+    if constexpr (EPI == S3_MASKBITS) {   // halfword (j0 >> 4) + f of the row, bits 4kq .. 4kq + 3
+      const int hi = (j0 >> 4) + f - 2 * (j0 >> 5);
+      const uint32_t m = (mw[a][hi >> 1] >> (16 * (hi & 1) + 4 * kq)) & 0xFu;
+      v[0] = (m & 1u) ? v[0] : 0.f; v[1] = (m & 2u) ? v[1] : 0.f;
+      v[2] = (m & 4u) ? v[2] : 0.f; v[3] = (m & 8u) ? v[3] : 0.f;
+      if constexpr (DROP) {
+        v[0] *= p.drop_inv; v[1] *= p.drop_inv; v[2] *= p.drop_inv; v[3] *= p.drop_inv;
+      }
+    }
+    const bool ok = row < p.M && col + 4 <= p.N;
+    const uint32_t off = ok ? 4u * (uint32_t)(row * p.ldc + col) : 0x80000000u;
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(s3_u32x4_t, v), c_rsrc, (int)off, 0, 0);
+    if (EPI == S3_RELU && p.bits) {   // the sign bitmask: row's 16 bits of fragment f from 4 lanes
+      uint32_t nib = (uint32_t)((acc[a][f][0] > 0.f) | ((acc[a][f][1] > 0.f) << 1) | ((acc[a][f][2] > 0.f) << 2) |
+                                ((acc[a][f][3] > 0.f) << 3));
+      if constexpr (DROP) nib = col < p.N ? nib & kb : 0u;   // (N % 4 == 0: a lane's columns are all in or all out)
+      // (rolled, the exchange sits between MFMAs: the VALU row swaps, not ds_bpermute — or_rows4)
+      constexpr bool kValuSwap = ROLL;
+      const uint32_t hw = or_rows4<kValuSwap>(nib << (4 * kq));
+      const int h = (j0 >> 4) + f;
+      if (kq == 0 && row < p.M && 16 * h < p.N) p.bits[(long long)row * p.ldbits + h] = (uint16_t)hw;
     }
   };
 
@@ -436,12 +516,19 @@ __global__ __launch_bounds__(512) void gemm_s3_nt_kernel(S3Params p) {
     };
     splitp(raA, pA);
     store_a(0, raA);
-    auto step_es = [&](int c, shortx8 (&P)[6], shortx8 (&Pn)[6], float4 (&R)[4], float4 (&F)[4]) {
-      load_a(c + 2, F);
-      asm volatile("" ::: "memory");   // the loads issue here, not sunk to the mid-step split
+    // `last` (ROLL): the last chunk's copy — no chunk c + 1 to split, no chunks c + 2 to fetch
+    // (the other copies fetch past KC, clamped, for one straight-line vmcnt count), no barrier, and
+    // fragment f - 1's epilogue after fragment f's MFMAs
+    auto step_es = [&](auto last, int c, shortx8 (&P)[6], shortx8 (&Pn)[6], float4 (&R)[4], float4 (&F)[4]) {
+      constexpr bool LAST = decltype(last)::value == 2, TAIL = decltype(last)::value != 0;
+      if constexpr (!LAST) {
+        load_a(c + 2, F);
+        asm volatile("" ::: "memory");   // the loads issue here, not sunk to the mid-step split
+      }
       // the fragments' LDS byte address: fragment f's rows 16f + cl sit 1,024 B apart (the
       // swizzle slot depends only on cl and kq), planes 13,312 B apart
-      const uint32_t b_addr = lds_base + 2u * (uint32_t)((c % 3) * kNtBuf + cl * 32 + 8 * nt_slot(cl, kq));
+      const int bcl = TAIL ? e_lane & 15 : cl, bkq = TAIL ? e_lane >> 4 : kq;
+      const uint32_t b_addr = lds_base + 2u * (uint32_t)((c % 3) * kNtBuf + bcl * 32 + 8 * nt_slot(bcl, bkq));
       // Each fragment's three plane reads as asm issued EPF fragments ahead, and an lgkmcnt
       // wait tied to its registers right before its MFMAs (hipcc, left alone, issued each pair
       // of fragments' reads just ahead of their MFMAs: the LDS latency in the MFMA stream once
@@ -469,21 +556,61 @@ __global__ __launch_bounds__(512) void gemm_s3_nt_kernel(S3Params p) {
           acc[0][f] = mfma_s3(P[0], P[1], P[2], bh, bm, bl, acc[0][f]);
           acc[1][f] = mfma_s3(P[3], P[4], P[5], bh, bm, bl, acc[1][f]);
         }
-        if (f == kNtEsAt) {
+        if constexpr (LAST) {
+          if (f >= 1) {
+            // every load of this wave has landed by now (the youngest, chunk KC's weights, was
+            // issued half a step ago): the bitmask words, and no DMA outlives the wave in LDS
+            if (f == 1) DL_WAIT_VMCNT(0);
+            epi_frag(0, f - 1);
+            epi_frag(1, f - 1);
+            asm volatile("" ::: "memory");   // ... here, not sunk below the next fragment's MFMAs
+          }
+        } else if (f == kNtEsAt) {
           if (c + 1 < KC) splitp(R, Pn);
           store_a(c + 1, R);   // (past KC: chunk KC's pieces fall outside the gathered chunks: dropped)
           dma_b(c + 2, (c + 2) % 3);
         }
       }
-      publish(c);
+      if constexpr (LAST) {
+        epi_frag(0, kNtNF - 1);
+        epi_frag(1, kNtNF - 1);
+      } else {
+        publish(c);
+      }
     };
+    constexpr std::integral_constant<int, 0> kBody{};
     int c = 0;
+    if constexpr (ROLL) {
+      constexpr std::integral_constant<int, 1> kTail{};   // a body step after the loop
+      constexpr std::integral_constant<int, 2> kLast{};
+      // KC >= 1 (every entry point refuses K < 8, s3_nt_check): there is always a last chunk
+      for (; c + 2 < KC; c += 2) {
+        step_es(kBody, c, pA, pB, raB, raA);
+        step_es(kBody, c + 1, pB, pA, raA, raB);
+      }
+      auto fresh_lane = [&]() {
+        e_lane = lane;
+        asm volatile("" : "+v"(e_lane));
+      };
+      fresh_lane();
+      if (c + 1 < KC) {
+        step_es(kTail, c, pA, pB, raB, raA);
+        fresh_lane();
+        load_mw();
+        step_es(kLast, c + 1, pB, pA, raA, raB);
+      } else {
+        load_mw();
+        step_es(kLast, c, pA, pB, raB, raA);
+      }
+      return;
+    } else {
     for (; c + 1 < KC; c += 2) {
-      step_es(c, pA, pB, raB, raA);
-      step_es(c + 1, pB, pA, raA, raB);
+      step_es(kBody, c, pA, pB, raB, raA);
+      step_es(kBody, c + 1, pB, pA, raA, raB);
     }
     load_mw();   // under the peeled last step's MFMAs (odd KC), else before the epilogue
-    if (c < KC) step_es(c, pA, pB, raB, raA);
+    if (c < KC) step_es(kBody, c, pA, pB, raB, raA);
+    }
   } else {
   // S3_MASK (the f32 ReluGrad mask): the plain step.  The host never pairs it with DIRECT, so
   // there is no transposed-accumulator arm here and no bitmask words to load.
@@ -532,56 +659,15 @@ __global__ __launch_bounds__(512) void gemm_s3_nt_kernel(S3Params p) {
   if (c < KC) step(c, raA);
   }
 
-  if constexpr (DIRECT) {
-    // lane (kq, cl): acc[a][f][j] = C[r0 + 16a + cl][j0 + 16f + 4kq + j].  Stores go through a
-    // buffer descriptor: a piece past M or N gets an offset past its range and is dropped.
-    const auto c_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.C, (short)0, p.M * p.ldc * 4, 0x00020000);
-    [[maybe_unused]] uint32_t d_step = 0;
-    [[maybe_unused]] uint2 d_key = make_uint2(0u, 0u);
+  if constexpr (DIRECT) {   // (not rolled: DROP, the training gather's plain-store form, or the A/B arm)
     if constexpr (DROP && EPI == S3_RELU) {
       d_step = drop_step(p.opt);
       d_key = make_uint2(p.drop_k0, p.drop_k1);
     }
 #pragma unroll
-    for (int a = 0; a < 2; ++a) {
-      const int row = r0 + 16 * a + cl;
+    for (int a = 0; a < 2; ++a)
 #pragma unroll
-      for (int f = 0; f < kNtNF; ++f) {
-        const int col = j0 + 16 * f + 4 * kq;
-        floatx4 v = acc[a][f];
-        if (EPI == S3_RELU) {
-          v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f);
-        }
-        [[maybe_unused]] uint32_t kb = 0xFu;
-        if constexpr (DROP && EPI == S3_RELU) {   // the lane's four columns are one Philox group
-          kb = drop_keep4((uint32_t)row, (uint32_t)col >> 2, p.drop_layer, d_step, d_key, p.drop_thr);
-          v[0] = (kb & 1u) ? v[0] * p.drop_inv : 0.f; v[1] = (kb & 2u) ? v[1] * p.drop_inv : 0.f;
-          v[2] = (kb & 4u) ? v[2] * p.drop_inv : 0.f; v[3] = (kb & 8u) ? v[3] * p.drop_inv : 0.f;
-        }
-        if constexpr (EPI == S3_MASKBITS) {   // halfword (j0 >> 4) + f of the row, bits 4kq .. 4kq + 3
-          const int hi = (j0 >> 4) + f - 2 * (j0 >> 5);
-          const uint32_t m = (mw[a][hi >> 1] >> (16 * (hi & 1) + 4 * kq)) & 0xFu;
-          v[0] = (m & 1u) ? v[0] : 0.f; v[1] = (m & 2u) ? v[1] : 0.f;
-          v[2] = (m & 4u) ? v[2] : 0.f; v[3] = (m & 8u) ? v[3] : 0.f;
-          if constexpr (DROP) {
-            v[0] *= p.drop_inv; v[1] *= p.drop_inv; v[2] *= p.drop_inv; v[3] *= p.drop_inv;
-          }
-        }
-        const bool ok = row < p.M && col + 4 <= p.N;
-        const uint32_t off = ok ? 4u * (uint32_t)(row * p.ldc + col) : 0x80000000u;
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(s3_u32x4_t, v), c_rsrc, (int)off, 0, 0);
-        if (EPI == S3_RELU && p.bits) {   // the sign bitmask: row's 16 bits of fragment f from 4 lanes
-          uint32_t nib = (uint32_t)((acc[a][f][0] > 0.f) | ((acc[a][f][1] > 0.f) << 1) | ((acc[a][f][2] > 0.f) << 2) |
-                                    ((acc[a][f][3] > 0.f) << 3));
-          if constexpr (DROP) nib = col < p.N ? nib & kb : 0u;   // (N % 4 == 0: a lane's columns are all in or all out)
-          uint32_t hw = nib << (4 * kq);
-          hw |= (uint32_t)__shfl_xor((int)hw, 16, 64);
-          hw |= (uint32_t)__shfl_xor((int)hw, 32, 64);
-          const int h = (j0 >> 4) + f;
-          if (kq == 0 && row < p.M && 16 * h < p.N) p.bits[(long long)row * p.ldbits + h] = (uint16_t)hw;
-        }
-      }
-    }
+      for (int f = 0; f < kNtNF; ++f) epi_frag(a, f);
     return;
   }
   // Epilogue through LDS (the ring is free after the last barrier): per wave and per half

@@ -1,16 +1,14 @@
 """GPU checks of batch normalisation in the deep tower (ModelSpec.batch_norm, csrc/bn.hip):
-the dl_bn_* kernels against the float64 formulas (tests/_bn_ref.py); five-step trajectories of one model
-of each family against the float64 restatement in every table mode, with the cross network and the
-attention, with sample weights and with one Adam launch per layer; predict on the running statistics,
-checkpoint, export and local_run; a poisoned step; and the unchanged kernel sequence at batch_norm off.
+the dl_bn_* kernels against the float64 formulas (tests/_bn_ref.py); the engine with one Adam launch per
+layer, a batch of one, predict on the running statistics and a poisoned step.  The other engine-level
+checks (trajectories of one model of each family, checkpoint, export, local_run, the unchanged kernel
+sequence at batch_norm off) are shared with the
+other options: their bodies run on the "bn" row of tests/_side_options.py, called from the last section
+here or collected as the [bn] cases of tests/test_gpu_side_options.py.
 
 Kernel shapes (B, D): (2, 1) the smallest; (63, 33) odd sizes, a partial column group, two row blocks;
 (300, 400) and (300, 416) the flagship's widths, a partial and a whole last halfword, ten row blocks;
 (4099, 50) 129 row blocks, a short last one."""
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 import torch
@@ -20,29 +18,16 @@ from deep_learning_amd._lib import call, ptr
 from deep_learning_amd.engine import CTREngine, ModelSpec
 from oracle import ctr_ref as R
 from tests import _bn_ref as Bn
-from tests import _sample_weight_ref as W
+from tests._side_options import (BN, B_, MODES, TOL, _batches, _bits, _check, _init, _run, _s,
+                                  default_queues_the_kernels_it_queued, follow, trajectory,
+                                  trajectory_matches_restatement, with_the)
+from tests._side_options import _engine as _side_engine
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-TOL = 1e-5          # absolute, against float64
 SHAPES = [(2, 1), (63, 33), (300, 400), (300, 416), (4099, 50)]
-KW = {"deepfm_pipeline": dict(C=13, V=3, S=8, E=8, cate_index_size=1000, hidden=[32, 16]),
-      "dnn_pipeline": dict(C=13, V=3, S=8, E=8, cate_index_size=1000, hidden=[32, 16]),
-      "dnn_multi_cate": dict(V=0, S=4, E=8, cate_index_size=1000, hidden=[32, 16],
-                             multi_ranges=[[0, 5, "a"], [5, 6, "b"]]),
-      "wdl": dict(C=13, S=8, E=8, cate_index_size=1000, hidden=[32, 16], Fw=4)}
-MODES = {"atomic": dict(bwd="atomic"), "sorted": dict(bwd="sorted"), "lazy": dict(adam="lazy")}
-B_ = 64
+KW = BN.KW
 FILL = -7.0
-
-
-def _s():
-    return _lib.stream_handle()
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.int32)
 
 
 # --------------------------------------------------------------------------- 1. the kernels
@@ -227,164 +212,29 @@ def test_bn_kernels_refuse_what_they_cannot_take(hip_lib):
     assert (t == 3).all() and (u == 3).all() and (small == 3).all()
 
 
-# --------------------------------------------------------------------------- 2. the engine
-def _batches(name, n, seed=11, B=B_):
-    return [Bn.make_batch(name, KW[name], B, seed + i) for i in range(n)]
-
-
-def _init(name, seed, L=0, A=0):
-    """Injected parameters at the models' init scales; gamma, beta off their initial 1 and 0."""
-    cfg = R.make_cfg(name, **KW[name])
-    return cfg, Bn.init_params(cfg, L, A, True, np.random.default_rng(seed), jitter=0.2)
-
-
-def _ref_run(name, P0, bs, L=0, A=0, per_step=None):
-    cfg = R.make_cfg(name, **KW[name])
-    P = {k: v.copy() for k, v in P0.items()}
-    opt = R.AdamTF1(cfg, P)
-    zs, losses = [], []
-    for i, b in enumerate(bs):
-        fw = Bn.train_step(cfg, P, opt, b, L, A, **(per_step(i, b) if per_step else {}))
-        zs.append(fw["z"])
-        losses.append(fw["loss"])
-    return zs, losses, P
-
-
-@pytest.fixture(scope="module")
-def trajectories():
-    """The restatement's five steps from injected parameters, once per model."""
-    out = {}
-    for name in KW:
-        _, P0 = _init(name, 42)
-        bs = _batches(name, 5)
-        out[name] = (P0, bs) + _ref_run(name, P0, bs)
-    return out
-
-
-def _run(eng, bs, graph_from=2):
-    zs, losses = [], []
-    for i, b in enumerate(bs):
-        eng.train_step(b, graph=i >= graph_from)
-        torch.cuda.synchronize()
-        zs.append(eng.z[: eng.last_batch].cpu().numpy().copy())
-        losses.append(eng.loss())
-    eng.check_error()
-    return zs, losses
-
-
-def _check(eng, got_z, got_l, zs, losses, P, tag):
-    err = dict(z=max(np.abs(a - b).max() for a, b in zip(got_z, zs)),
-               loss=max(abs(a - b) for a, b in zip(got_l, losses)))
-    got = eng.params()
-    assert set(got) == set(P), set(got) ^ set(P)
-    bn = [k for k in P if k.startswith("batch_norm")]
-    assert len(bn) == 4 * len(eng.spec.hidden) and all(got[k].shape == P[k].shape for k in bn)
-    err["params"] = max(np.abs(got[k] - P[k]).max() for k in P if k not in bn)
-    err["biases"] = max(np.abs(got[k] - P[k]).max() for k in P if k.startswith("deep_bias_"))
-    err["gamma_beta"] = max(np.abs(got[k] - P[k]).max() for k in bn if not "running" in k)
-    err["running"] = max(np.abs(got[k] - P[k]).max() for k in bn if "running" in k)
-    print(tag, "max |engine - restatement|:", {k: float(v) for k, v in err.items()})
-    for k, v in err.items():
-        assert v < TOL, (k, v)
-    return got
-
-
+# --------------------------------------------------------------------------- 2. the engine, what only bn has
 def _engine(name, P0, mode="lazy", **spec_kw):
-    ekw = dict(MODES[mode])
     sw = spec_kw.pop("sample_weight", False)
-    eng = CTREngine(ModelSpec(name, batch_norm=True, **spec_kw, **KW[name]), max_batch=B_, init="none",
-                    sample_weight=sw, **ekw)
+    eng = _side_engine(BN, name, spec=spec_kw, init="none", sample_weight=sw, **MODES[mode])
     eng.load_params({k: v.copy() for k, v in P0.items()})
     return eng
 
 
-@pytest.mark.parametrize("name", list(KW))
-def test_trajectory_matches_restatement(hip_lib, trajectories, name):
-    """Five steps (two eager, three replayed as a hipGraph) in every table mode: each step's logits and
-    loss, the final parameters, gamma / beta and the running statistics within 1e-5 of the restatement;
-    lazy and sorted + dense bit for bit (dnn_pipeline, deepfm_pipeline)."""
-    P0, bs, zs, losses, P = trajectories[name]
-    res = {}
-    for mode in MODES:
-        eng = _engine(name, P0, mode)
-        gz, gl = _run(eng, bs)
-        res[mode] = (gz, _check(eng, gz, gl, zs, losses, P, "%s %s" % (name, mode)), eng.dense_state())
-    k = Bn.KEY % (1, "weight")
-    for mv in ("m", "v"):
-        assert np.abs(res["lazy"][2][mv][k]).max() > 0
-    if name in ("dnn_pipeline", "deepfm_pipeline"):
-        for a, b in zip(res["lazy"][0], res["sorted"][0]):
-            np.testing.assert_array_equal(a, b)
-        for k in res["lazy"][1]:
-            np.testing.assert_array_equal(res["lazy"][1][k], res["sorted"][1][k], err_msg=k)
-        for mv in ("m", "v"):
-            for k in Bn.bn_keys(R.make_cfg(name, **KW[name]), running=False):
-                np.testing.assert_array_equal(res["lazy"][2][mv][k], res["sorted"][2][mv][k])
-    # the layer does matter, and every piece of its state moved
-    assert np.abs(P[Bn.KEY % (2, "running_mean")] - P0[Bn.KEY % (2, "running_mean")]).max() > 100 * TOL
-    assert np.abs(P[Bn.KEY % (1, "weight")] - P0[Bn.KEY % (1, "weight")]).max() > 100 * TOL
-
-
-def test_with_the_cross_network_and_the_attention(hip_lib):
-    name = "dnn_multi_cate"
-    _, P0 = _init(name, 43, L=2, A=4)
-    bs = _batches(name, 5, seed=15)
-    zs, losses, P = _ref_run(name, P0, bs, L=2, A=4)
-    eng = _engine(name, P0, afm_attention=4, cross_layers=2)
-    gz, gl = _run(eng, bs)
-    _check(eng, gz, gl, zs, losses, P, "cross + afm + bn")
-
-
-def test_sample_weights(hip_lib):
-    """sample_weight=True and pos_weight 2.5 (weights in {0, 0.5, 1, 3}): the statistics stay unweighted
-    (a zero-weight row counts in mu and var), the loss is the weighted one."""
-    name, pw = "deepfm_pipeline", 2.5
-    _, P0 = _init(name, 6)
-    bs = _batches(name, 5, seed=31)
-    for i, b in enumerate(bs):
-        b["weight"] = np.random.default_rng(90 + i).choice(np.float32([0, 0.5, 1, 3]), B_).reshape(B_, 1)
-    per_step = lambda i, b: dict(w=W.w_eff_f32(b["weight"], b["label"], pw)[0])
-    zs, losses, P = _ref_run(name, P0, bs, per_step=per_step)
-    eng = _engine(name, P0, pos_weight=pw, sample_weight=True)
-    gz, gl = _run(eng, bs)
-    _check(eng, gz, gl, zs, losses, P, "weighted")
-
-
-def test_one_adam_launch_per_layer(hip_lib, trajectories, monkeypatch):
+def test_one_adam_launch_per_layer(hip_lib, monkeypatch):
     monkeypatch.setenv("DLAMD_ADAM_FUSED", "0")
     name = "dnn_pipeline"
-    P0, bs, zs, losses, P = trajectories[name]
+    P0, bs, zs, losses, P = trajectory(BN, name)
     eng = _engine(name, P0)
     assert not eng._adam_fused()
     gz, gl = _run(eng, bs)
-    _check(eng, gz, gl, zs, losses, P, "adam per layer")
-
-
-def test_same_seed_runs_agree_bit_for_bit(hip_lib):
-    name = "wdl"
-    bs = _batches(name, 5, seed=3)
-    out = []
-    for _ in range(2):
-        eng = CTREngine(ModelSpec(name, batch_norm=True, **KW[name]), max_batch=B_, seed=7, adam="lazy")
-        p0 = eng.params()
-        zs, _ = _run(eng, bs, graph_from=0)
-        out.append((zs, eng.params(), eng.dense_state(), p0))
-    for a, b in zip(out[0][0], out[1][0]):
-        np.testing.assert_array_equal(a, b)
-    for k in out[0][1]:
-        np.testing.assert_array_equal(out[0][1][k], out[1][1][k], err_msg=k)
-    k = Bn.KEY % (2, "bias")
-    np.testing.assert_array_equal(out[0][2]["v"][k], out[1][2]["v"][k])
-    p0 = out[0][3]
-    assert (p0[Bn.KEY % (1, "weight")] == 1).all() and (p0[Bn.KEY % (1, "bias")] == 0).all()
-    assert (p0[Bn.KEY % (1, "running_mean")] == 0).all() and (p0[Bn.KEY % (1, "running_var")] == 1).all()
+    _check(BN, eng, gz, gl, zs, losses, P, "adam per layer")
 
 
 def test_batch_of_one_is_refused_before_anything_is_queued(hip_lib, monkeypatch):
     from deep_learning_amd import engine as E
     name = "dnn_pipeline"
     eng = CTREngine(ModelSpec(name, batch_norm=True, **KW[name]), max_batch=B_, seed=3)
-    b = {k: v[:1] for k, v in _batches(name, 1)[0].items()}
+    b = {k: v[:1] for k, v in _batches(BN, name, 1)[0].items()}
     names = []
     real = E.call
     monkeypatch.setattr(E, "call", lambda n, *a: (names.append(n), real(n, *a))[1])
@@ -394,16 +244,15 @@ def test_batch_of_one_is_refused_before_anything_is_queued(hip_lib, monkeypatch)
     assert eng.predict(b).shape == (1,)
 
 
-# --------------------------------------------------------------------------- 3. predict and persistence
 def test_predict_uses_the_running_statistics(hip_lib):
     """After training, predict equals the restatement in eval mode within 1e-5 and differs from a
     train-mode forward on the same batch by more than 1e-3; lazy tables: predict after training, after
     flush() and on flush(planes=True)'s planes (unfused: layer 0 stores its pre-activation) agree bit
     for bit."""
     name = "dnn_pipeline"
-    _, P0 = _init(name, 9)
+    _, P0 = _init(BN, name, 9)
     eng = _engine(name, P0)
-    bs = _batches(name, 6, seed=40)
+    bs = _batches(BN, name, 6, seed=40)
     for b in bs[:3]:
         eng.train_step(b, graph=True)
     torch.cuda.synchronize()
@@ -430,62 +279,14 @@ def test_predict_uses_the_running_statistics(hip_lib):
         np.testing.assert_array_equal(run[k], after[k])
 
 
-def test_checkpoint_and_export_round_trip(hip_lib, tmp_path):
-    """A checkpoint saved after three steps and restored into a fresh model continues to step five bit
-    for bit (logits, every parameter, the running statistics, gamma's and beta's moments); the exported
-    model loads with batch_norm and scores identically."""
-    import types
-    from deep_learning_amd.models._ctr_model import export_model, load_model
-    from deep_learning_amd.models.dnn_pipeline import DeepModel
-    kw = KW["dnn_pipeline"]
-    args = types.SimpleNamespace(epochs=1, batch_size=B_, model_pb=str(tmp_path / "pb"),
-                                 save_model_checkpoint=str(tmp_path / "ck"), model_restore=0,
-                                 restore_model_checkpoint=str(tmp_path / "ck"), embedding_size=kw["E"],
-                                 cate_feats_size=kw["cate_index_size"], hidden_units=kw["hidden"], learning_rate=1e-3,
-                                 l2_reg=1e-5, learning_rate_decay_steps=1000, learning_rate_decay_rate=0.9,
-                                 cate_field_size=kw["S"], cont_field_size=kw["C"], vector_feats_size=kw["V"],
-                                 batch_norm=True, bn_momentum=0.2)
-    bs = _batches("dnn_pipeline", 5, seed=60)
-    a = DeepModel(args, bs)
-    a.model_optimizer()
-    assert a.engine.bn and a.engine.spec.bn_momentum == 0.2
-    for b in bs[:3]:
-        a.engine.train_step(b, graph=True)
-    a._save_checkpoint(args.save_model_checkpoint)
-    r = DeepModel(args, bs)
-    r.model_optimizer()
-    r._restore(args.restore_model_checkpoint)
-    for m in (a, r):
-        m.zs = []
-        for b in bs[3:]:
-            m.engine.train_step(b, graph=True)
-            torch.cuda.synchronize()
-            m.zs.append(m.engine.z[:B_].cpu().numpy().copy())
-    for x, y in zip(a.zs, r.zs):
-        np.testing.assert_array_equal(x, y)
-    pa, pr = a.engine.params(), r.engine.params()
-    assert np.abs(pa[Bn.KEY % (1, "running_mean")]).max() > 0
-    for k in pa:
-        np.testing.assert_array_equal(pa[k], pr[k], err_msg=k)
-    sa, sr = a.engine.dense_state(), r.engine.dense_state()
-    for mv in ("m", "v"):
-        for k in (Bn.KEY % (1, "weight"), Bn.KEY % (2, "bias")):
-            assert np.abs(sa[mv][k]).max() > 0
-            np.testing.assert_array_equal(sa[mv][k], sr[mv][k])
-    export_model(a.engine, args.model_pb)
-    loaded = load_model(args.model_pb)
-    assert loaded.spec.batch_norm is True and loaded.bn and loaded.spec.bn_momentum == 0.2
-    np.testing.assert_array_equal(loaded.predict(bs[0]), a.engine.predict(bs[0]))
-
-
 def test_poisoned_step_leaves_the_layer_alone(hip_lib):
     """A batch with an out-of-range id: gamma, beta, their moments and the running statistics keep
     their bits; the next batch applies normally."""
     name = "dnn_pipeline"
-    _, P0 = _init(name, 12)
+    _, P0 = _init(BN, name, 12)
     for mode in ("atomic", "lazy"):
         eng = _engine(name, P0, mode)
-        bs = _batches(name, 3, seed=80)
+        bs = _batches(BN, name, 3, seed=80)
         eng.train_step(bs[0])
         torch.cuda.synchronize()
         eng.check_error()
@@ -515,65 +316,21 @@ def test_poisoned_step_leaves_the_layer_alone(hip_lib):
         assert all(np.abs(p3[k] - p2[k]).max() > 0 for k in keys)
 
 
-def test_local_run_train_then_predict(hip_lib, tmp_path):
-    """local_run.py dnn_pipeline ... batch_norm=1: train -> export -> predict end to end; the exported
-    variables hold the layer's four arrays and the printed AUC is the restatement's (eval mode) on them
-    within 1e-4."""
-    from deep_learning_amd.synthetic import make_batch
-    from deep_learning_amd.utils import data_loader
-    conf, tr, pr = tmp_path / "conf", tmp_path / "train", tmp_path / "pred"
-    for p in (conf, tr, pr):
-        p.mkdir()
-    lines = ["f%d\tx\tfloat" % i for i in range(13)] + ["c%d\tx\tstring" % i for i in range(26)]
-    (conf / "dnn.conf").write_text("\n".join(lines) + "\n")
-    V = 3000
-    for i in range(3):
-        data_loader.write_tfrecord_part(str(tr / ("part-%d" % i)), make_batch(256, cate_index_size=V, seed=i))
-    pred_part = make_batch(200, cate_index_size=V, seed=99)
-    data_loader.write_tfrecord_part(str(pr / "part-0"), pred_part)
-    args = ["dnn_pipeline", "train", "1", "8", str(V), "3", str(conf), str(tr) + "/", str(pr) + "/",
-            str(tmp_path / "model_pb"), str(tmp_path / "ckpt"), "0", str(tmp_path / "ckpt"),
-            "batch_size=64", "hidden_units=32,16", "shuffle=0", "batch_norm=1", "bn_momentum=0.3"]
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "local_run.py")] + args, capture_output=True, text=True,
-                       timeout=900, cwd=ROOT)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
-    auc_gpu = float(r.stdout.split("val of auc:")[-1].split()[0])
-    d = np.load(tmp_path / "model_pb" / "variables.npz")
-    P = {k: d[k] for k in d.files}
-    assert P[Bn.KEY % (1, "running_var")].shape == (32,) and P[Bn.KEY % (2, "weight")].shape == (16,)
-    assert np.abs(P[Bn.KEY % (1, "running_mean")]).max() > 0
-    kw = dict(C=13, V=0, S=26, E=8, cate_index_size=V, hidden=[32, 16])
-    b = {k: v[:192] for k, v in pred_part.items()}
-    ref = Bn.forward_backward(R.make_cfg("dnn_pipeline", **kw), P, b, bn=True, train=False)
-    assert abs(R.auc(b["label"], ref["p"]) - auc_gpu) < 1e-4
+# --------------------------------------------------------------------------- the engine: the shared bodies
+# (tests/_side_options.py) on this option's row
+@pytest.mark.parametrize("name", list(BN.KW))
+def test_trajectory_matches_restatement(hip_lib, name):
+    trajectory_matches_restatement(BN, name)
 
 
-# --------------------------------------------------------------------------- 4. the default
-@pytest.mark.parametrize("name,adam", [("dnn_pipeline", "dense"), ("dnn_pipeline", "lazy"), ("wdl", "lazy")])
+def test_with_the_cross_network_and_the_attention(hip_lib):
+    with_the(BN, "the_cross_network_and_the_attention")
+
+
+def test_sample_weights(hip_lib):
+    follow(BN, BN.weighted)
+
+
+@pytest.mark.parametrize("name,adam", BN.defaults)
 def test_default_queues_the_kernels_it_queued(hip_lib, name, adam, monkeypatch):
-    """batch_norm off: a step's and a predict's entry-point sequence equals that of an engine built
-    without the argument, and holds none of the new entry points or buffers; with it on, the same
-    sequence plus the new launches."""
-    from deep_learning_amd import engine as E
-    names = []
-    real = E.call
-    monkeypatch.setattr(E, "call", lambda n, *a: (names.append(n), real(n, *a))[1])
-    bs = _batches(name, 2, seed=70)
-    seqs = []
-    for extra in ({}, {"batch_norm": False}, {"batch_norm": True}):
-        eng = CTREngine(ModelSpec(name, **extra, **KW[name]), max_batch=B_, seed=3, adam=adam)
-        del names[:]
-        eng.train_step(bs[0])
-        eng.predict(bs[1])
-        torch.cuda.synchronize()
-        seqs.append(list(names))
-        if not extra.get("batch_norm"):
-            assert eng.bn_groups == [] and not any(hasattr(eng, a) for a in ("bn_run", "bn_stat", "hx", "bn_ws"))
-    assert seqs[0] == seqs[1] and len(seqs[0]) > 8
-    assert not any("dl_bn" in n for n in seqs[0])
-    rest = list(seqs[2])
-    nl = 2      # per layer: the step's stats, finish, sums, apply, bias row and Adam, predict's finish
-    for n in nl * ["dl_bn_stats", "dl_bn_fwd", "dl_bn_bwd_sums", "dl_bn_bwd_apply", "dl_bn_zero_bias_grad",
-                   "dl_adam_dense", "dl_bn_fwd"]:
-        rest.remove(n)
-    assert rest == seqs[0]
+    default_queues_the_kernels_it_queued(BN, name, adam, monkeypatch)
